@@ -7,7 +7,8 @@ BASELINE.json configs[1], 1M single-choice 5-option ballots.  With N ranks each 
 shard (weak scaling; ballots are independent, no data-path collective) and the per-rank tallies are
 all-gathered over RCCL once per step.
 
-    python bench.py --gpus 1 --steps 5 --warmup 1
+    python bench.py --gpus 1 --steps 5 --warmup 1          # the headline line alone: set-up, warm-up, the timed steps
+    python bench.py --gpus 1 --steps 5 --warmup 1 --full   # ... and every leg, check and roofline beyond it
     python bench.py --gpus N --steps K --warmup W          # bare: starts the N ranks itself, as a child torch.distributed.run
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
@@ -189,9 +190,42 @@ def parse():
                          "gets, PCIe included; the line says so (config.input = host) and is never the headline")
     ap.add_argument("--selfbench-seconds", type=float, default=2.0,
                     help="length of the field-multiplication calibration run before the timed region (valu_roofline.box); 0 = skip")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the calibration run, kernel profiles and rooflines, clock sampling, "
+                         "the untimed isolated step, the PCIe-inclusive and wire-ingest legs, per-rank figures, the tally and verdict "
+                         "checks, the CPU baseline and the extra configs (the --no-* options and --selfbench-seconds select among "
+                         "them).  Without it a run sets up, warms up, times the steps and prints the headline line; it then cannot "
+                         "fail on a wrong tally (exit 5); only the checks of a multi-rank run before its timed steps still end a job early")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step (verdict words, tally encoding; "
+                         "msm: the products) as DIR/<name>.npy in float64, at most 64 MB in all")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     args.box_fmul_g = None           # set by the calibration run (valu_roofline.box); the extra configs quote their fractions against it
     return args
+
+
+DUMP_BYTES = 64_000_000           # --dump-outputs: all .npy files of one run together stay below this
+
+
+def dump_outputs(path, arrays: dict, budget: int = DUMP_BYTES):
+    """--dump-outputs: the arrays the timed path handed its caller in its last step, as <path>/<name>.npy in float64 (status words and
+    bytes are exact in it).  An array that does not fit its share of `budget` is written as a fixed, seeded sample of its rows in
+    ascending order, their indices in <name>_rows.npy: the same rows in every run with the same arguments."""
+    import numpy as np
+
+    out = Path(path)
+    out.mkdir(parents=True, exist_ok=True)
+    share = budget // len(arrays) - 4096                   # room for the .npy headers
+    for name, a in arrays.items():
+        a = np.asarray(a).astype(np.float64)
+        if a.nbytes > share:
+            row = a.nbytes // a.shape[0]
+            keep = np.sort(np.random.default_rng(0).choice(a.shape[0], size=share // (row + 8), replace=False))
+            np.save(out / f"{name}_rows.npy", keep.astype(np.float64))
+            a = a[keep]
+        np.save(out / f"{name}.npy", a)
 
 
 def cpu_model() -> str:
@@ -276,6 +310,9 @@ def bench_msm(args, ctx, eg, torch, dev, world):
     m = measure_msm(args, ctx, eg, torch, dev, args.steps, args.warmup)
     n, big, elapsed, double_ms, big_ms = m["n"], m["big"], m["elapsed"], m["double_ms"], m["big_ms"]
     k, p, r, bk, bp, out1, ok1, out2 = m["bufs"]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"double_mul": out1.view(n, 32).cpu().numpy(), "double_mul_ok": ok1.cpu().numpy(),
+                                         "multi_mul_65536": out2.cpu().numpy()})
     value = n / (double_ms * 1e-3)
     line = {
         "metric": "Group::vartime_double_mul_generator operations/sec (Ristretto backend, primitive tier)",
@@ -294,7 +331,7 @@ def bench_msm(args, ctx, eg, torch, dev, world):
                      "note": "algorithmic bytes per operation: two scalars, a point, an encoding = 128 B against ~2600 field "
                              "multiplications: VALU-bound like the batch tier"},
     }
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         from oracle import oracle as o
 
         hk, hp, hr = bytes(k.cpu().numpy()), bytes(p.cpu().numpy()), bytes(r.cpu().numpy())
@@ -691,20 +728,46 @@ def bench_in_process(args):
 
     for _ in range(args.warmup):
         step()
-    sampler = ClockSampler(torch, devs[0])
-    sampler.start()
+    sampler = ClockSampler(torch, devs[0]) if args.full else None
+    if sampler:
+        sampler.start()
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
     for dev_i in set(devs):
         torch.cuda.synchronize(dev_i)
     elapsed = time.perf_counter() - t0
-    clock = sampler.stop()
+    clock = sampler.stop() if sampler else None
+    if args.dump_outputs:
+        import numpy as np
+
+        got = (host_status[:total].cpu().numpy() if args.from_host
+               else np.concatenate([st[:c].cpu().numpy() for st, c in zip(status, counts)]))
+        dump_outputs(args.dump_outputs, {"status": got.view(np.uint32), "tally": np.frombuffer(merged[0], dtype=np.uint8)})
+    n_tampered = sum(int(c * args.tampered_percent / 100.0) for c in counts)
+    out = {
+        "metric": "EncryptedChoice ballot verifications/sec" if args.workload != "qv" else "QuadraticVotingBallot verifications/sec",
+        "value": total * args.steps / elapsed, "unit": "ballots/s", "n_gpus": N, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "strong" if strong else "weak", "vs_baseline": None,
+        "dtype": "u32", "data": "synthetic",
+        "config": {"workload": f"{counts[0]} {args.workload} {n_opt}-option ballots per GPU per step, resident in HBM; verify + homomorphic tally "
+                               f"+ in-library tally merge over {N} GPUs of ONE process (eg_verify_*_batch_multi_device)",
+                   "ballots_per_gpu": counts[0], "total_ballots": total, "options": n_opt, "ballot_bytes": params[0].ballot_size,
+                   "seed": args.seed, "tampered": n_tampered, "generator_s": round(gen_s, 3),
+                   "parallelism": f"in-process{N}" + ("-on-one-gpu" if args.rehearse_one_gpu else ""), "devices": devs,
+                   "input": "host" if args.from_host else "hbm"},
+    }
+    if args.from_host:
+        out["config"]["workload"] = (f"{total} {args.workload} {n_opt}-option ballots in ONE pinned host buffer per step; eg_verify_*_batch_multi cuts it "
+                                     f"into {N} contiguous slabs, uploads and verifies each on its GPU (one host thread per GPU inside the library), "
+                                     "merges the tallies: PCIe-INCLUSIVE, not the headline metric")
+    if not args.full:
+        print(json.dumps(out), flush=True)
+        return
     if args.from_host:
         accepted = int((host_status[:total] == 0).sum().item())
     else:
         accepted = sum(int((st[:c] == 0).sum().item()) for st, c in zip(status, counts))
-    n_tampered = sum(int(c * args.tampered_percent / 100.0) for c in counts)
     # the merged tally is the sum of the per-GPU running tallies, each of which is the tally of its own slab: re-merge them with the
     # primitive tier one by one, and (one GPU's worth of work, untimed) let ONE engine verify every slab and compare its running tally
     grp = eg.Ristretto(ctxs[0])
@@ -722,24 +785,9 @@ def bench_in_process(args):
             torch.cuda.set_device(devs[0])
             one.verify_batch_device(c, src.data_ptr(), scratch.data_ptr(), 0)
         tally_ok = tally_ok and one.tally_encode() == merged[0]
-    out = {
-        "metric": "EncryptedChoice ballot verifications/sec" if args.workload != "qv" else "QuadraticVotingBallot verifications/sec",
-        "value": total * args.steps / elapsed, "unit": "ballots/s", "n_gpus": N, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "strong" if strong else "weak", "vs_baseline": None,
-        "dtype": "u32", "data": "synthetic",
-        "config": {"workload": f"{counts[0]} {args.workload} {n_opt}-option ballots per GPU per step, resident in HBM; verify + homomorphic tally "
-                               f"+ in-library tally merge over {N} GPUs of ONE process (eg_verify_*_batch_multi_device)",
-                   "ballots_per_gpu": counts[0], "total_ballots": total, "options": n_opt, "ballot_bytes": params[0].ballot_size,
-                   "seed": args.seed, "accepted": accepted, "tampered": n_tampered, "tally_exchange_ok": bool(tally_ok),
-                   "tally_checked_against_one_engine": check_one_engine, "generator_s": round(gen_s, 3),
-                   "parallelism": f"in-process{N}" + ("-on-one-gpu" if args.rehearse_one_gpu else ""), "devices": devs,
-                   "input": "host" if args.from_host else "hbm"},
-        "clock": clock,
-    }
+    out["config"].update({"accepted": accepted, "tally_exchange_ok": bool(tally_ok), "tally_checked_against_one_engine": check_one_engine})
+    out["clock"] = clock
     if args.from_host:
-        out["config"]["workload"] = (f"{total} {args.workload} {n_opt}-option ballots in ONE pinned host buffer per step; eg_verify_*_batch_multi cuts it "
-                                     f"into {N} contiguous slabs, uploads and verifies each on its GPU (one host thread per GPU inside the library), "
-                                     "merges the tallies: PCIe-INCLUSIVE, not the headline metric")
         out["host_inclusive"] = {"value": out["value"], "unit": "ballots/s", "bytes_h2d": total * params[0].ballot_size, "bytes_d2h": 4 * total,
                                  "pinned": True, "h2d_gb_per_s": total * params[0].ballot_size * args.steps / elapsed / 1e9,
                                  "note": "`value` of this line IS the PCIe-inclusive rate (first H2D byte to last status byte D2H, every step)"}
@@ -904,7 +952,7 @@ def main():
     # warm-up and outside the timed region: the shipped fe_mul in a bare chain for --selfbench-seconds (eg_selfbench_fmul)
     dev_index = dev.index if dev.index is not None else 0
     box = None
-    if args.selfbench_seconds > 0:
+    if args.full and args.selfbench_seconds > 0:
         barrier()
         bs = ClockSampler(torch, dev_index)
         bs.start()
@@ -918,20 +966,68 @@ def main():
         except eg.EgError as e:             # a calibration must never cost the line
             bs.stop()
             box = {"error": repr(e)}
-    ctx.profile_enable(True)
-    ctx.profile_read()
-    ctx.profile_read_tables()
-    sampler = ClockSampler(torch, dev_index)       # every rank samples its own GPU (`per_rank`); rank 0's is the line's `clock`
+    if args.full:
+        ctx.profile_enable(True)
+        ctx.profile_read()
+        ctx.profile_read_tables()
+    sampler = ClockSampler(torch, dev_index) if args.full else None   # every rank samples its own GPU (`per_rank`); rank 0's is the line's `clock`
     barrier()
-    sampler.start()
+    if sampler:
+        sampler.start()
     t0 = time.perf_counter()
     for k in range(args.steps):
-        step(k)
+        step(k if args.full else None)
     torch.cuda.synchronize()
     own_elapsed = time.perf_counter() - t0            # this rank's own steps, before it waits for the others
     barrier()
     elapsed = time.perf_counter() - t0
-    clock = sampler.stop()
+    clock = sampler.stop() if sampler else None
+    if args.dump_outputs:                             # every rank its own slab's verdicts; the exchanged tally is the same on every rank
+        import numpy as np
+
+        mine = {"status" if world == 1 else f"status_rank{rank}": status.cpu().numpy().view(np.uint32)}
+        if rank == 0:
+            mine["tally"] = final_tally.cpu().numpy()
+        dump_outputs(args.dump_outputs, mine, DUMP_BYTES // world)
+    elapsed = egd.max_over_ranks(elapsed, dev)
+    value = total * args.steps / elapsed
+    ms_per_step = elapsed / args.steps * 1e3
+    out = {
+        "metric": "EncryptedChoice ballot verifications/sec" if args.workload != "qv" else "QuadraticVotingBallot verifications/sec",
+        "value": value,
+        "unit": "ballots/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms_per_step,
+        "higher_is_better": True,
+        "scaling": "strong" if strong else "weak",
+        "vs_baseline": None,
+        "dtype": "u32",
+        "data": "synthetic",
+        "config": {
+            "workload": {
+                "single": f"{B} single-choice {n_opt}-option EncryptedChoice ballots per GPU per step, resident in HBM "
+                          "(BASELINE.json configs[1]); verify + homomorphic tally + tally all-gather",
+                "multi": f"{B} multi-choice 3-of-{n_opt} EncryptedChoice ballots per GPU per step (BASELINE.json configs[3])",
+                "qv": f"{B} QuadraticVotingBallot ballots, {n_opt} options / {args.credits} credits (BASELINE.json configs[2])",
+            }[args.workload],
+            "ballots_per_gpu": B,
+            "total_ballots": total,
+            "options": n_opt,
+            "ballot_bytes": params.ballot_size,
+            "seed": args.seed,
+            "tampered": n_tampered * world,
+            "generator_s": round(gen_s, 3),
+            "parallelism": f"shard{world}" if world > 1 else "single",
+        },
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if use_dist:
+            dist.destroy_process_group()
+        return
     exchange_ms = sum(a.elapsed_time(b) for a, b in ex_ev[: args.steps]) / max(args.steps, 1)
     msm_ms, msm_launches, all_ms = ctx.profile_read()
     tables_ms, tables_launches = ctx.profile_read_tables()
@@ -945,13 +1041,10 @@ def main():
         iso_ms, iso_launches, _ = ctx.profile_read()
         iso_tables_ms, iso_tables_launches = ctx.profile_read_tables()
     ctx.profile_enable(False)
-    elapsed = egd.max_over_ranks(elapsed, dev)
 
     accepted = int((status == 0).sum().item())
     tally_ok = exchange_consistent()          # again after the timed steps (and the only check of a one-rank run)
     accepted_all = egd.sum_over_ranks(accepted, dev)
-    value = total * args.steps / elapsed
-    ms_per_step = elapsed / args.steps * 1e3
 
     # ---- legs that EVERY rank runs at the same time when there are several (the scaling risk is host-side staging - N x 736 MB
     # through one host's memory and PCIe root - not the 320-byte collective): the PCIe-inclusive rate of each rank's own slab from a pinned
@@ -1011,38 +1104,8 @@ def main():
         traffic_bpbl = None
     iso_units = -(-B // max(1, iso_launches // n_stages)) if iso_launches else 0
     iso_achieved = alg_bytes * iso_units / (iso_ms / iso_launches * 1e-3) / 1e9 if iso_launches else 0.0
-    out = {
-        "metric": "EncryptedChoice ballot verifications/sec" if args.workload != "qv" else "QuadraticVotingBallot verifications/sec",
-        "value": value,
-        "unit": "ballots/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": ms_per_step,
-        "higher_is_better": True,
-        "scaling": "strong" if strong else "weak",
-        "vs_baseline": None,
-        "dtype": "u32",
-        "data": "synthetic",
-        "config": {
-            "workload": {
-                "single": f"{B} single-choice {n_opt}-option EncryptedChoice ballots per GPU per step, resident in HBM "
-                          "(BASELINE.json configs[1]); verify + homomorphic tally + tally all-gather",
-                "multi": f"{B} multi-choice 3-of-{n_opt} EncryptedChoice ballots per GPU per step (BASELINE.json configs[3])",
-                "qv": f"{B} QuadraticVotingBallot ballots, {n_opt} options / {args.credits} credits (BASELINE.json configs[2])",
-            }[args.workload],
-            "ballots_per_gpu": B,
-            "total_ballots": total,
-            "options": n_opt,
-            "ballot_bytes": params.ballot_size,
-            "chunk_ballots": chunk,
-            "seed": args.seed,
-            "accepted": accepted_all,
-            "tally_exchange_ok": bool(tally_ok),
-            "tampered": n_tampered * world,
-            "generator_s": round(gen_s, 3),
-            "parallelism": f"shard{world}" if world > 1 else "single",
-        },
+    out["config"].update({"chunk_ballots": chunk, "accepted": accepted_all, "tally_exchange_ok": bool(tally_ok)})
+    out.update({
         "roofline": {
             "bound": "hbm",
             "kernel": dominant,
@@ -1084,7 +1147,7 @@ def main():
                     "HBM fraction is ~1e-3 by construction (SURVEY 0.6); the binding roof is VALU integer multiply-add "
                     "throughput, see DESIGN.md",
         },
-    }
+    })
 
     if True:
         narrow_bits, wide_bits = ctx.comb_table_bits()        # wide comb tables exist once an engine has seen 2^19 items

@@ -243,6 +243,39 @@ def test_gpus_are_counted_without_hip(tmp_path):
     assert bench.count_gpus_without_hip(str(tmp_path / "absent"), {}) is None
 
 
+def test_bench_options_and_output_dump(tmp_path, monkeypatch):
+    """bench.py's --full is off by default, --steps below 1 is refused, and --dump-outputs writes float64 arrays that stay within the
+    budget: an array too large for its share becomes a fixed, seeded sample of its rows, their indices beside it."""
+    import importlib.util
+    import sys
+
+    import numpy as np
+
+    spec = importlib.util.spec_from_file_location("bench_for_test", ROOT / "bench.py")
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    args = bench.parse()
+    assert args.steps == 7 and args.warmup == 2 and args.full is False and args.dump_outputs is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+
+    status = np.arange(1000, dtype=np.uint32) * 4_000_000            # verdict words use all 32 bits
+    tally = np.arange(320, dtype=np.uint64).astype(np.uint8)
+    bench.dump_outputs(tmp_path / "a", {"status": status, "tally": tally})
+    assert np.load(tmp_path / "a" / "status.npy").dtype == np.float64
+    assert np.array_equal(np.load(tmp_path / "a" / "status.npy"), status) and np.array_equal(np.load(tmp_path / "a" / "tally.npy"), tally)
+    assert not (tmp_path / "a" / "status_rows.npy").exists()
+    big = np.arange(300_000 * 4, dtype=np.uint32).reshape(300_000, 4)
+    for d in ("b", "c"):
+        bench.dump_outputs(tmp_path / d, {"big": big, "tally": tally}, budget=2_000_000)
+    rows = np.load(tmp_path / "b" / "big_rows.npy").astype(np.int64)
+    assert np.array_equal(rows, np.load(tmp_path / "c" / "big_rows.npy")) and np.all(np.diff(rows) > 0)
+    assert np.array_equal(np.load(tmp_path / "b" / "big.npy"), big[rows]) and len(rows) > 10_000
+    assert sum(f.stat().st_size for f in (tmp_path / "b").iterdir()) <= 2_000_000
+
+
 def test_abi_version_and_release_counter_without_a_gpu(lib_path):
     """Two entry points that need no GPU: eg_abi_version is the header's EG_ABI_VERSION (and the Python binding's), and the ready-made
     release function of eg_verify_json_feed_owned counts into the size_t it is given (NULL: does nothing)."""

@@ -40,7 +40,7 @@ def test_bench_started_bare_launches_its_own_ranks():
     """`python3 bench.py --gpus 2 ...` with no launcher and no WORLD_SIZE: bench.py starts the two ranks itself as a child
     torch.distributed.run (before it has touched the GPU), the child's one JSON line is the last line of stdout, exit code 0
     (VERDICT r4 task 1; the loop over voters of examples/voting.rs:199-203 cut into N slabs)."""
-    r = _run_bare(["--gpus", "2", "--rehearse-one-gpu", "--steps", "1", "--warmup", "0", "--ballots", "20000", "--cpu-seconds", "1",
+    r = _run_bare(["--full", "--gpus", "2", "--rehearse-one-gpu", "--steps", "1", "--warmup", "0", "--ballots", "20000", "--cpu-seconds", "1",
                    "--selfbench-seconds", "0.5"])
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     out = r.stdout.strip().splitlines()
@@ -74,8 +74,8 @@ def test_bench_spawned_single_rank_goes_through_the_bare_launch_path_over_rccl()
     `python -m torch.distributed.run`, the rank initialises RCCL (backend nccl, world size 1), runs the preflight all-gather and the
     steps, and prints ONE line with tally_exchange_ok (examples/voting.rs:199-203 is the loop the slabs stand in for).  A second
     invocation asks for one GPU more than HIP_VISIBLE_DEVICES leaves visible: refused with exit code 2 before any rank starts."""
-    r = _run_bare(["--gpus", "1", "--force-dist", "--spawn", "--steps", "1", "--warmup", "0", "--ballots", "20000", "--selfbench-seconds", "0.5",
-                   "--cpu-seconds", "1", "--no-extra-configs"])
+    r = _run_bare(["--full", "--gpus", "1", "--force-dist", "--spawn", "--steps", "1", "--warmup", "0", "--ballots", "20000",
+                   "--selfbench-seconds", "0.5", "--cpu-seconds", "1", "--no-extra-configs"])
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     out = r.stdout.strip().splitlines()
     lines = [l for l in out if l.startswith("{")]
@@ -96,7 +96,7 @@ def test_bench_in_process_devices_rehearsed():
     process).  Weak (3 x 30 000, 1 % tampered) and strong (100 001 ballots cut in three)."""
     for extra, total, tampered in ((["--ballots", "30000", "--tampered-percent", "1"], 90000, 900),
                                    (["--total-ballots", "100001", "--workload", "qv"], 100001, 0)):
-        r = _run_bare(["--in-process-devices", "3", "--rehearse-one-gpu", "--steps", "2", "--warmup", "1", *extra],
+        r = _run_bare(["--full", "--in-process-devices", "3", "--rehearse-one-gpu", "--steps", "2", "--warmup", "1", *extra],
                       {"EG_CHUNK": "32768", "EG_COMB_BIG_BITS": "0"})
         assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
         lines = [l for l in r.stdout.strip().splitlines() if l.startswith("{")]
@@ -112,7 +112,7 @@ def test_bench_in_process_devices_rehearsed():
         assert js["devices"] == 3 and js["verdicts_match_device_path"] is True and js["value"] > 1e4, js
     # the same through ONE pinned host buffer (--from-host: eg_verify_*_batch_multi; VERDICT r5 task 1): the entry a one-process host
     # with its ballots in host memory calls had no timing anywhere
-    r = _run_bare(["--in-process-devices", "3", "--rehearse-one-gpu", "--from-host", "--steps", "2", "--warmup", "1", "--ballots", "30000",
+    r = _run_bare(["--full", "--in-process-devices", "3", "--rehearse-one-gpu", "--from-host", "--steps", "2", "--warmup", "1", "--ballots", "30000",
                    "--tampered-percent", "1"], {"EG_CHUNK": "32768", "EG_COMB_BIG_BITS": "0"})
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     line = json.loads([l for l in r.stdout.strip().splitlines() if l.startswith("{")][-1])
@@ -125,7 +125,7 @@ def test_bench_four_ranks_ten_million_ballots_rehearsed():
     """BASELINE configs[4] - 10 M single-choice ballots, sharded, 1 % tampered, ONE tally exchange - with four ranks time-sharing the
     GPU (gloo for the exchange), per-rank memory bounded (chunks of 65 536 ballots, narrow comb tables): shards of 2.5 M each,
     9 900 000 accepted, the exchanged tally identical on every rank, one JSON line from rank 0 (examples/voting.rs:199-203)."""
-    r = _run(4, ["--steps", "1", "--warmup", "0", "--rehearse-one-gpu", "--total-ballots", "10000000", "--tampered-percent", "1",
+    r = _run(4, ["--full", "--steps", "1", "--warmup", "0", "--rehearse-one-gpu", "--total-ballots", "10000000", "--tampered-percent", "1",
                  "--no-isolated"], {"EG_CHUNK": "65536", "EG_COMB_BIG_BITS": "0"})
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.strip().splitlines() if l.startswith("{")]

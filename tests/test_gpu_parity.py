@@ -1644,7 +1644,7 @@ def test_bench_rccl_leg_in_a_fresh_process():
     """The N > 1 code path of bench.py on the one GPU of the box: torch.distributed over RCCL is initialised for a single
     rank, the tally goes through tally_encode_device -> all_gather_into_tensor -> eg_points_sum_device on the shared stream,
     and must come out equal to the engine's own tally (examples/voting.rs:199-203 is what the exchange stands in for)."""
-    line = _run_bench("--gpus", "1", "--force-dist", "--ballots", "131072", "--steps", "1", "--warmup", "0", "--no-cpu-baseline")
+    line = _run_bench("--full", "--gpus", "1", "--force-dist", "--ballots", "131072", "--steps", "1", "--warmup", "0", "--no-cpu-baseline")
     assert line["config"]["tally_exchange_ok"] is True
     assert line["config"]["accepted"] == 131072 and line["n_gpus"] == 1 and line["scaling"] == "weak"
     assert line["roofline"]["frac"] > 0 and line["value"] > 1e5
@@ -1669,7 +1669,7 @@ def test_bench_two_ranks_rehearsed_on_one_gpu(mode):
         env.pop(k, None)
     size = ["--ballots", "60000"] if mode == "weak" else ["--total-ballots", "100001"]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(29700 + os.getpid() % 200), str(root / "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+           "--master-port", str(29700 + os.getpid() % 200), str(root / "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1",
            "--rehearse-one-gpu", "--tampered-percent", "1", "--selfbench-seconds", "0.5", "--cpu-seconds", "2", *size]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=str(root))
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
@@ -1753,10 +1753,61 @@ def test_two_ranks_real_gpu_tallies(eg, ctx, pk, tmp_path):
 
 def test_bench_fixed_total_mode():
     """`--total-ballots N` (BASELINE.json configs[4]: a fixed batch sharded over the ranks) with 1 % tampered ballots."""
-    line = _run_bench("--gpus", "1", "--total-ballots", "300000", "--tampered-percent", "1", "--steps", "1", "--warmup", "0",
+    line = _run_bench("--full", "--gpus", "1", "--total-ballots", "300000", "--tampered-percent", "1", "--steps", "1", "--warmup", "0",
                       "--no-cpu-baseline", "--no-host-inclusive")
     assert line["scaling"] == "strong" and line["config"]["total_ballots"] == 300000
     assert line["config"]["accepted"] == 300000 - 3000 and line["config"]["tally_exchange_ok"] is True
+
+
+def test_bench_plain_run_dumps_what_its_last_step_computed(oracle, pk, tmp_path):
+    """Without --full bench.py prints the headline line alone; --dump-outputs writes the verdict words and the exchanged tally of the last
+    timed step, which must be the oracle's on the same seeded ballots (1 % tampered, as bench.py tampers them).  The in-process path's
+    dump and the primitive tier's products are checked against the oracle the same way."""
+    import numpy as np
+    import torch
+
+    n, seed = 4096, 20260612
+    line = _run_bench("--gpus", "1", "--ballots", str(n), "--tampered-percent", "1", "--steps", "3", "--warmup", "1",
+                      "--dump-outputs", str(tmp_path / "single"))
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["value"] > 0 and line["unit"] == "ballots/s"
+    assert line["higher_is_better"] is True and line["dtype"] == "u32"
+    assert not {"roofline", "valu_roofline", "cpu_baseline", "host_inclusive", "wire_ingest", "extra"} & set(line)
+    op = oracle.ChoiceParams(pk, 5, True)
+    ballots = bytearray(op.generate_batch(seed, 0, n, threads=8))
+    bad = torch.randperm(n, generator=torch.Generator(device="cpu").manual_seed(seed))[: n // 100].tolist()
+    for i in bad:
+        ballots[(i + 1) * op.ballot_size - 32] ^= 1
+    want = op.verify_batch(bytes(ballots), threads=8)
+    status = np.load(tmp_path / "single" / "status.npy")
+    tally = np.load(tmp_path / "single" / "tally.npy")
+    assert status.dtype == np.float64 and status.tolist() == want and sorted(np.flatnonzero(status).tolist()) == sorted(bad)
+    assert bytes(tally.astype(np.uint8)) == op.tally(bytes(ballots), want)
+
+    _run_bench("--in-process-devices", "2", "--rehearse-one-gpu", "--ballots", str(n // 2), "--steps", "2", "--warmup", "1",
+               "--dump-outputs", str(tmp_path / "in_process"))
+    clean = op.generate_batch(seed, 0, n, threads=8)
+    assert not np.load(tmp_path / "in_process" / "status.npy").any()
+    assert bytes(np.load(tmp_path / "in_process" / "tally.npy").astype(np.uint8)) == op.tally(clean, [0] * n)
+
+    line = _run_bench("--gpus", "1", "--workload", "msm", "--ballots", "2048", "--steps", "1", "--warmup", "1",
+                      "--dump-outputs", str(tmp_path / "msm"))
+    assert line["steps"] == 1 and "cpu_baseline" not in line
+    prod = np.load(tmp_path / "msm" / "double_mul.npy")
+    assert prod.shape == (2048, 32) and np.load(tmp_path / "msm" / "double_mul_ok.npy").min() == 1
+    g = torch.Generator(device="cpu").manual_seed(seed)
+
+    def scalars(count):                  # bench.py's measure_msm draws its operands from one seeded generator, in this order
+        t = torch.randint(0, 256, (count, 32), dtype=torch.uint8, generator=g)
+        t[:, 31] &= 0x0F
+        return t.numpy().tobytes()
+
+    k, r, x = scalars(2048), scalars(2048), scalars(2048)          # [k]P + [r]G with P = [x]G
+    bk, bx = scalars(1 << 16), scalars(1 << 16)                    # one 65 536-term product over points [x]G
+    for i in range(2048):
+        p = oracle.point_mul_generator(x[32 * i : 32 * i + 32])
+        assert bytes(prod[i].astype(np.uint8)) == oracle.point_double_mul_generator(k[32 * i : 32 * i + 32], p, r[32 * i : 32 * i + 32]), i
+    bp = b"".join(oracle.point_mul_generator(bx[32 * i : 32 * i + 32]) for i in range(1 << 16))
+    assert bytes(np.load(tmp_path / "msm" / "multi_mul_65536.npy").astype(np.uint8)) == oracle.point_multi_mul(bk, bp)
 
 
 def test_host_buffer_path_matches_device_path(eg, ctx, pk):

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Turns the outputs of tools/profile_round.sh (under gpurun_out/) into the summaries kept under profiles/:
+"""Turns the outputs of tools/profile_round.sh (under $PROFILE_OUT, default profile_out/) into the summaries kept under profiles/:
    <round>_bench_line*.json, <round>_kernel_stats_<workload>.txt, <round>_pmc_counters.txt and traffic.json (the memory-side
    bytes per ballot and launch of every profiled kernel, which bench.py reads for `roofline.traffic`).
    usage: profile_summary.py [--traffic-only] <round-tag, e.g. r03>
@@ -9,13 +9,14 @@ import collections
 import csv
 import hashlib
 import json
+import os
 import shutil
 import subprocess
 import sys
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent.parent
-OUT = ROOT / "gpurun_out"
+OUT = ROOT / os.environ.get("PROFILE_OUT", "profile_out")
 PROF = ROOT / "profiles"
 args = [a for a in sys.argv[1:] if not a.startswith("--")]
 TRAFFIC_ONLY = "--traffic-only" in sys.argv[1:]
