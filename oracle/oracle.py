@@ -57,6 +57,11 @@ def _declare(l: C.CDLL) -> None:
         "or_merlin_append_u64": (None, [vp, u8p, C.c_uint64]),
         "or_merlin_challenge": (None, [vp, u8p, u8p, C.c_size_t]),
         "or_keccak_calls": (C.c_uint64, []),
+        "or_script_set": (None, [C.c_size_t, C.POINTER(C.c_int), u8p]),
+        "or_script_trace": (None, [C.c_int]),
+        "or_script_trace_read": (C.c_size_t, [C.POINTER(C.c_int), C.c_size_t]),
+        "or_diag_read": (None, [u64p]),
+        "or_diag_reset": (None, []),
         "or_rng_seed_from_u64": (None, [C.POINTER(ChaChaRng), C.c_uint64]),
         "or_rng_fill64": (None, [C.POINTER(ChaChaRng), u8p]),
         "or_keypair_from_seed": (None, [C.c_uint64, u8p, u8p, C.POINTER(ChaChaRng)]),
@@ -244,6 +249,58 @@ def keypair_from_seed(seed: int):
     sk, pk, rng = _buf(32), _buf(32), ChaChaRng()
     lib().or_keypair_from_seed(seed, sk, pk, C.byref(rng))
     return sk.raw, pk.raw, rng
+
+
+# --------------------------------------------------------------------------- scripted randomness, verifier counters
+L = 2**252 + 27742317777372353535851937790883648493
+ROLES = {"key": 1, "ct_r": 2, "value_r": 3, "ring_nonce": 4, "ring_response": 5, "logeq_nonce": 6,
+         "sumsq_ez": 7, "sumsq_er": 8, "sumsq_ex": 9}
+_ROLE_NAMES = {v: k for k, v in ROLES.items()}
+
+
+class Script:
+    """Scripted randomness for the provers (eg_oracle.h, OR_ROLE_*).  Inside ``with Script(pins) as s:`` a draw whose role
+    (name, scope, i, k) is a key of `pins` returns the pinned scalar (an int, taken mod l, or 32 bytes); every other draw returns
+    what the ChaCha stream gives without a script, because pinned draws advance the stream too.  Afterwards s.trace lists the
+    role of every draw made in the block, in order.  Roles: ct_r (scope, ciphertext i), value_r (scope), ring_nonce (scope, ring i),
+    ring_response (scope, ring i, index k), logeq_nonce, sumsq_ez, sumsq_er (i), sumsq_ex (i), key.  scope is the option of a QV
+    vote's range proof (n_options: the credit range proof) and 0 everywhere else.  Pins and trace belong to the calling thread."""
+
+    def __init__(self, pins=None):
+        self.pins = dict(pins or {})
+        self.trace = []
+
+    def __enter__(self):
+        roles, values = [], b""
+        for (name, *idx), v in self.pins.items():
+            idx = list(idx) + [0] * (3 - len(idx))
+            roles += [ROLES[name]] + idx
+            values += v if isinstance(v, bytes) else (v % L).to_bytes(32, "little")
+        arr = (C.c_int * max(len(roles), 1))(*roles)
+        lib().or_script_set(len(self.pins), arr, values or b"\0")
+        lib().or_script_trace(1)
+        return self
+
+    def __exit__(self, *exc):
+        n = lib().or_script_trace_read(None, 0)
+        buf = (C.c_int * max(4 * n, 1))()
+        lib().or_script_trace_read(buf, n)
+        self.trace = [(_ROLE_NAMES[buf[4 * j]], buf[4 * j + 1], buf[4 * j + 2], buf[4 * j + 3]) for j in range(n)]
+        lib().or_script_trace(0)
+        lib().or_script_set(0, None, None)
+        return False
+
+
+def diag_reset() -> None:
+    lib().or_diag_reset()
+
+
+def diag() -> dict:
+    """Identity elements the verifiers of this thread met since diag_reset(): recomputed commitments, ciphertext elements of ring
+    and sum-of-squares proofs, and the elements log-equality / sum-of-squares proofs run over (eg_oracle.h, OR_DIAG_*)."""
+    out = (C.c_uint64 * 3)()
+    lib().or_diag_read(out)
+    return {"commitment": out[0], "ciphertext": out[1], "base": out[2]}
 
 
 # --------------------------------------------------------------------------- params objects

@@ -13,6 +13,13 @@
 #include <stdlib.h>
 #include <string.h>
 
+/* ------------------------------------------------------------------ diagnostic counters (per thread, like or_keccak_calls) */
+
+static __thread uint64_t g_diag[OR_DIAG_N];
+void or_diag_read(uint64_t out[OR_DIAG_N]) { memcpy(out, g_diag, sizeof g_diag); }
+void or_diag_reset(void) { memset(g_diag, 0, sizeof g_diag); }
+static void diag_id(int which, const ge *p) { g_diag[which] += (uint64_t)or_ge_is_identity(p); }
+
 /* ------------------------------------------------------------------ keys */
 
 int or_pubkey_from_bytes(or_pubkey *pk, const uint8_t b[32]) {
@@ -36,6 +43,11 @@ int or_logeq_verify(const or_pubkey *pk, const ge *p0, const ge *p1, const sc *c
   sc ks[2] = {neg_c, *response};
   ge ps[2] = {*p1, pk->element};
   or_ge_multi_mul(&c1, 2, ks, ps); /* :161-164 */
+  diag_id(OR_DIAG_ID_BASE, p0);
+  diag_id(OR_DIAG_ID_BASE, p1);
+  diag_id(OR_DIAG_ID_BASE, &pk->element);
+  diag_id(OR_DIAG_ID_COMMITMENT, &c0);
+  diag_id(OR_DIAG_ID_COMMITMENT, &c1);
 
   or_t_start_proof(t, "log_eq");
   or_merlin_append(t, "K", pk->bytes, 32);
@@ -65,6 +77,8 @@ int or_ring_verify(const or_pubkey *pk, int n_rings, const int *sizes, const ge 
   size_t start = 0;
   for (int ring = 0; ring < n_rings; ring++) {
     const ge *R = &cts[2 * ring], *B = &cts[2 * ring + 1];
+    diag_id(OR_DIAG_ID_CIPHERTEXT, R);
+    diag_id(OR_DIAG_ID_CIPHERTEXT, B);
     sc challenge = *common_challenge;
     ge cg, ck;
     or_ge_generator(&cg);
@@ -88,6 +102,8 @@ int or_ring_verify(const or_pubkey *pk, int n_rings, const int *sizes, const ge 
       sc ks[2] = {*response, neg_e};
       ge ps[2] = {pk->element, dh};
       or_ge_multi_mul(&ck, 2, ks, ps); /* :347-350 */
+      diag_id(OR_DIAG_ID_COMMITMENT, &cg);
+      diag_id(OR_DIAG_ID_COMMITMENT, &ck);
       if (eq + 1 < sizes[ring]) { /* :354-360 */
         merlin_t et = rt;
         or_merlin_append_u64(&et, "j", (uint64_t)eq);
@@ -269,6 +285,10 @@ static int sumsq_verify_decoded(const or_pubkey *pk, int n, const ge *cts, const
     ge ps[3] = {g, pk->element, *X};
     or_ge_multi_mul(&e_x, 3, ks, ps);
     or_t_append_element(&t, "[e_x]G + [e_r]K", &e_x);
+    diag_id(OR_DIAG_ID_CIPHERTEXT, Rx);
+    diag_id(OR_DIAG_ID_CIPHERTEXT, X);
+    diag_id(OR_DIAG_ID_COMMITMENT, &e_r);
+    diag_id(OR_DIAG_ID_COMMITMENT, &e_x);
   }
   /* :232-247 */
   sc *ks = (sc *)malloc(sizeof(sc) * (size_t)(n + 2));
@@ -286,6 +306,10 @@ static int sumsq_verify_decoded(const or_pubkey *pk, int n, const ge *cts, const
   ps[n + 1] = sum_ct[1];
   or_ge_multi_mul(&e_z, (size_t)(n + 2), ks, ps);
   free(ks); free(ps);
+  diag_id(OR_DIAG_ID_BASE, &sum_ct[0]);
+  diag_id(OR_DIAG_ID_BASE, &sum_ct[1]);
+  diag_id(OR_DIAG_ID_COMMITMENT, &e_rz);
+  diag_id(OR_DIAG_ID_COMMITMENT, &e_z);
 
   or_t_append_element(&t, "R_z", &sum_ct[0]); /* :249-253 */
   or_t_append_element(&t, "Z", &sum_ct[1]);

@@ -26,9 +26,58 @@ static void ensure_ktable(or_pubkey *pk) {
   if (!pk->ktable) pk->ktable = or_fixed_table_new(&pk->element);
 }
 
+/* ------------------------------------------------------------------ scripted randomness (test infrastructure)
+ * Every scalar the provers draw has a ROLE (OR_ROLE_*, with a scope and two indices).  A caller may pin the value returned for a
+ * role (or_script_set); the ChaCha stream advances on every draw whether it is pinned or not, so the draws that are not pinned
+ * return what they return without a script.  The trace lists the role of every draw, so that tests do not depend on draw order.
+ * Pins and trace are per thread. */
+typedef struct { int role[4]; sc value; } pin_t;
+static __thread pin_t *g_pins;
+static __thread size_t g_n_pins;
+static __thread int g_trace_on;
+static __thread int *g_trace;
+static __thread size_t g_trace_len, g_trace_cap;
+
+void or_script_set(size_t n, const int *roles, const uint8_t *values) {
+  free(g_pins);
+  g_pins = n ? (pin_t *)malloc(sizeof(pin_t) * n) : NULL;
+  g_n_pins = n;
+  for (size_t i = 0; i < n; i++) {
+    memcpy(g_pins[i].role, roles + 4 * i, sizeof g_pins[i].role);
+    memcpy(g_pins[i].value.b, values + 32 * i, 32);
+  }
+}
+
+void or_script_trace(int on) {
+  g_trace_on = on;
+  g_trace_len = 0;
+}
+
+size_t or_script_trace_read(int *out, size_t cap) {
+  size_t n = g_trace_len < cap ? g_trace_len : cap;
+  if (out && n) memcpy(out, g_trace, sizeof(int) * 4 * n);
+  return g_trace_len;
+}
+
+static void draw(chacha_rng *rng, sc *out, int role, int scope, int i, int k) {
+  or_rng_scalar(rng, out);
+  if (g_trace_on) {
+    if (g_trace_len == g_trace_cap) {
+      g_trace_cap = g_trace_cap ? 2 * g_trace_cap : 256;
+      g_trace = (int *)realloc(g_trace, sizeof(int) * 4 * g_trace_cap);
+    }
+    int *t = g_trace + 4 * g_trace_len++;
+    t[0] = role; t[1] = scope; t[2] = i; t[3] = k;
+  }
+  for (size_t p = 0; p < g_n_pins; p++) {
+    const int *r = g_pins[p].role;
+    if (r[0] == role && r[1] == scope && r[2] == i && r[3] == k) { *out = g_pins[p].value; return; }
+  }
+}
+
 void or_keypair_generate(chacha_rng *rng, sc *sk, or_pubkey *pk) {
   /* Keypair::generate -> SecretKey::generate (one generate_scalar draw), pk = [sk]G */
-  or_rng_scalar(rng, sk);
+  draw(rng, sk, OR_ROLE_KEY, 0, 0, 0);
   or_ge_mul_generator(&pk->element, sk);
   or_ristretto_encode(pk->bytes, &pk->element);
   pk->ktable = NULL;
@@ -38,8 +87,8 @@ void or_keypair_generate(chacha_rng *rng, sc *sk, or_pubkey *pk) {
 /* ExtendedCiphertext (encryption.rs:303-327) */
 typedef struct { ge R, B; sc r; } ext_ct;
 
-static void ext_ct_new(ext_ct *c, const ge *value, const or_pubkey *pk, chacha_rng *rng) {
-  or_rng_scalar(rng, &c->r);
+static void ext_ct_new(ext_ct *c, const ge *value, const or_pubkey *pk, chacha_rng *rng, int role, int scope, int i) {
+  draw(rng, &c->r, role, scope, i, 0);
   or_ge_mul_generator(&c->R, &c->r);
   ge dh;
   mul_k(&dh, pk, &c->r);
@@ -56,6 +105,7 @@ typedef struct {
   sc *responses;
   ge term_g, term_k;
   sc discrete_log, random_scalar;
+  int scope; /* of the scripted draws */
 } ring_t;
 
 static void ring_commitments(ge *cg, ge *ck, const ring_t *ring, const or_pubkey *pk, int eq,
@@ -75,8 +125,9 @@ static void ring_commitments(ge *cg, ge *ck, const ring_t *ring, const or_pubkey
 
 static void ring_new(ring_t *ring, int index, const or_pubkey *pk, const ext_ct *ct,
                      const ge *admissible, int size, int value_index, const merlin_t *transcript,
-                     sc *responses, chacha_rng *rng) {
+                     sc *responses, chacha_rng *rng, int scope) {
   /* ring.rs:54-131 */
+  ring->scope = scope;
   ring->index = index;
   ring->size = size;
   ring->value_index = value_index;
@@ -93,7 +144,7 @@ static void ring_new(ring_t *ring, int index, const or_pubkey *pk, const ext_ct 
   or_merlin_append(&ring->transcript, "enc", enc, 64);
   or_merlin_append_u64(&ring->transcript, "i", (uint64_t)index);
 
-  or_rng_scalar(rng, &ring->random_scalar);
+  draw(rng, &ring->random_scalar, OR_ROLE_RING_NONCE, scope, index, 0);
   ge cg, ck;
   or_ge_mul_generator(&cg, &ring->random_scalar);
   mul_k(&ck, pk, &ring->random_scalar);
@@ -104,7 +155,7 @@ static void ring_new(ring_t *ring, int index, const or_pubkey *pk, const ext_ct 
     or_t_append_element(&et, "R_K", &ck);
     sc challenge;
     or_t_challenge_scalar(&et, "c", &challenge);
-    or_rng_scalar(rng, &responses[eq]);
+    draw(rng, &responses[eq], OR_ROLE_RING_RESPONSE, scope, index, eq);
     ring_commitments(&cg, &ck, ring, pk, eq, &responses[eq], &challenge);
   }
   ring->term_g = cg;
@@ -115,7 +166,7 @@ static void ring_finalize(ring_t *ring, const or_pubkey *pk, const sc *common, c
   /* ring.rs:162-194 */
   sc challenge = *common;
   for (int eq = 0; eq < ring->value_index; eq++) {
-    or_rng_scalar(rng, &ring->responses[eq]);
+    draw(rng, &ring->responses[eq], OR_ROLE_RING_RESPONSE, ring->scope, ring->index, eq);
     ge cg, ck;
     ring_commitments(&cg, &ck, ring, pk, eq, &ring->responses[eq], &challenge);
     merlin_t et = ring->transcript;
@@ -136,27 +187,29 @@ typedef struct {
   sc *responses;
   size_t used;
   chacha_rng *rng;
+  int scope;
 } builder_t;
 
-static void builder_init(builder_t *b, const or_pubkey *pk, sc *responses, merlin_t *t, chacha_rng *rng, int max_rings) {
+static void builder_init(builder_t *b, const or_pubkey *pk, sc *responses, merlin_t *t, chacha_rng *rng, int max_rings,
+                         int scope) {
   /* ring.rs:442-457 */
   or_t_start_proof(t, "multi_ring_enc");
   or_merlin_append(t, "K", pk->bytes, 32);
-  b->pk = pk; b->transcript = t; b->n_rings = 0; b->responses = responses; b->used = 0; b->rng = rng;
+  b->pk = pk; b->transcript = t; b->n_rings = 0; b->responses = responses; b->used = 0; b->rng = rng; b->scope = scope;
   b->rings = (ring_t *)malloc(sizeof(ring_t) * (size_t)(max_rings > 0 ? max_rings : 1));
 }
 
 static void builder_add_precomputed(builder_t *b, const ext_ct *ct, const ge *adm, int size, int vi) {
   /* ring.rs:471-492 */
   ring_new(&b->rings[b->n_rings], b->n_rings, b->pk, ct, adm, size, vi, b->transcript,
-           b->responses + b->used, b->rng);
+           b->responses + b->used, b->rng, b->scope);
   b->used += (size_t)size;
   b->n_rings++;
 }
 
 static void builder_add_value(builder_t *b, const ge *adm, int size, int vi, ext_ct *out) {
   /* ring.rs:460-469 */
-  ext_ct_new(out, &adm[vi], b->pk, b->rng);
+  ext_ct_new(out, &adm[vi], b->pk, b->rng, OR_ROLE_CT_R, b->scope, b->n_rings);
   builder_add_precomputed(b, out, adm, size, vi);
 }
 
@@ -173,14 +226,14 @@ static void builder_build(builder_t *b, sc *common) {
 /* ------------------------------------------------------------------ LogEqualityProof::new */
 
 static void logeq_new(const or_pubkey *pk, const sc *secret, const ge *p0, const ge *p1,
-                      merlin_t *t, chacha_rng *rng, sc *challenge, sc *response) {
+                      merlin_t *t, chacha_rng *rng, sc *challenge, sc *response, int scope) {
   /* log_equality.rs:114-139 */
   or_t_start_proof(t, "log_eq");
   or_merlin_append(t, "K", pk->bytes, 32);
   or_t_append_element(t, "[r]G", p0);
   or_t_append_element(t, "[r]K", p1);
   sc x;
-  or_rng_scalar(rng, &x);
+  draw(rng, &x, OR_ROLE_LOGEQ_NONCE, scope, 0, 0);
   ge xg, xk;
   or_ge_mul_generator(&xg, &x);
   mul_k(&xk, pk, &x);
@@ -203,7 +256,7 @@ void or_encrypt_u64(const or_pubkey *pk, uint64_t value, chacha_rng *rng, uint8_
   ext_ct c;
   or_sc_from_u64(&v, value);
   or_ge_mul_generator(&vg, &v);
-  ext_ct_new(&c, &vg, pk, rng);
+  ext_ct_new(&c, &vg, pk, rng, OR_ROLE_CT_R, 0, 0);
   put_ct(out, &c.R, &c.B);
 }
 
@@ -211,13 +264,13 @@ void or_encrypt_zero(const or_pubkey *pk, chacha_rng *rng, uint8_t out[128]) {
   /* keys/impls.rs:30-51 */
   sc r;
   ge R, B;
-  or_rng_scalar(rng, &r);
+  draw(rng, &r, OR_ROLE_CT_R, 0, 0, 0);
   or_ge_mul_generator(&R, &r);
   mul_k(&B, pk, &r);
   put_ct(out, &R, &B);
   merlin_t t;
   or_merlin_init(&t, "zero_encryption");
-  logeq_new(pk, &r, &R, &B, &t, rng, (sc *)(out + 64), (sc *)(out + 96));
+  logeq_new(pk, &r, &R, &B, &t, rng, (sc *)(out + 64), (sc *)(out + 96), 0);
 }
 
 void or_encrypt_bool(const or_pubkey *pk, int value, chacha_rng *rng, uint8_t out[160]) {
@@ -230,7 +283,7 @@ void or_encrypt_bool(const or_pubkey *pk, int value, chacha_rng *rng, uint8_t ou
   sc responses[2];
   memset(responses, 0, sizeof responses);
   builder_t *b = (builder_t *)malloc(sizeof(builder_t));
-  builder_init(b, pk, responses, &t, rng, 1);
+  builder_init(b, pk, responses, &t, rng, 1, 0);
   ext_ct c;
   builder_add_value(b, adm, 2, value ? 1 : 0, &c);
   builder_build(b, (sc *)(out + 64));
@@ -251,7 +304,7 @@ void or_choice_new(const or_choice_params *p, const uint8_t *flags, chacha_rng *
   merlin_t t;
   or_merlin_init(&t, "encrypted_choice_ranges");
   builder_t *b = (builder_t *)malloc(sizeof(builder_t));
-  builder_init(b, &p->pk, responses, &t, rng, n);
+  builder_init(b, &p->pk, responses, &t, rng, n, 0);
   ge sum_r, sum_b;
   sc sum_rand;
   or_ge_identity(&sum_r);
@@ -275,7 +328,7 @@ void or_choice_new(const or_choice_params *p, const uint8_t *flags, chacha_rng *
     merlin_t ts;
     or_merlin_init(&ts, "choice_encryption_sum");
     uint8_t *sum_proof = ring_proof + 32 * (size_t)(1 + 2 * n);
-    logeq_new(&p->pk, &sum_rand, &sum_r, &p1, &ts, rng, (sc *)sum_proof, (sc *)(sum_proof + 32));
+    logeq_new(&p->pk, &sum_rand, &sum_r, &p1, &ts, rng, (sc *)sum_proof, (sc *)(sum_proof + 32), 0);
   }
   free(b->rings); free(b);
   free(responses);
@@ -285,14 +338,14 @@ void or_choice_new(const or_choice_params *p, const uint8_t *flags, chacha_rng *
 
 /* returns the value ciphertext (with randomness) and writes ct || partials || ring proof */
 static void range_new(const or_pubkey *pk, const or_prepared_range *r, uint64_t value,
-                      const char *label, chacha_rng *rng, uint8_t *out, ext_ct *out_ct) {
+                      const char *label, chacha_rng *rng, uint8_t *out, ext_ct *out_ct, int scope) {
   /* range.rs:462-534 */
   sc v;
   ge vg;
   or_sc_from_u64(&v, value);
   or_ge_mul_generator(&vg, &v);
   ext_ct ct;
-  ext_ct_new(&ct, &vg, pk, rng); /* CiphertextWithValue::new, encryption.rs:403-407 */
+  ext_ct_new(&ct, &vg, pk, rng, OR_ROLE_VALUE_R, scope, 0); /* CiphertextWithValue::new, encryption.rs:403-407 */
   int idx[OR_MAX_RINGS];
   or_range_decompose(&r->d, value, idx);
   merlin_t t;
@@ -301,7 +354,7 @@ static void range_new(const or_pubkey *pk, const or_prepared_range *r, uint64_t 
   or_merlin_append(&t, "range", (const uint8_t *)r->name, (size_t)r->name_len);
   sc *responses = (sc *)calloc((size_t)r->total_size, sizeof(sc));
   builder_t *b = (builder_t *)malloc(sizeof(builder_t));
-  builder_init(b, pk, responses, &t, rng, OR_MAX_RINGS);
+  builder_init(b, pk, responses, &t, rng, OR_MAX_RINGS, scope);
   ext_ct cum;
   or_ge_identity(&cum.R);
   or_ge_identity(&cum.B);
@@ -332,7 +385,7 @@ static void range_new(const or_pubkey *pk, const or_prepared_range *r, uint64_t 
 void or_encrypt_range(const or_pubkey *pk, const or_prepared_range *r, uint64_t value,
                       chacha_rng *rng, uint8_t *out) {
   /* keys/impls.rs:120-129 */
-  range_new(pk, r, value, "ciphertext_range", rng, out, NULL);
+  range_new(pk, r, value, "ciphertext_range", rng, out, NULL, 0);
 }
 
 /* ------------------------------------------------------------------ SumOfSquaresProof::new */
@@ -345,16 +398,16 @@ static void sumsq_new(const or_pubkey *pk, int n, const ext_ct *cts, const uint6
   or_t_start_proof(&t, "sum_of_squares");
   or_merlin_append(&t, "K", pk->bytes, 32);
   sc e_z, sum_rand = sum_ct->r;
-  or_rng_scalar(rng, &e_z); /* :116 */
+  draw(rng, &e_z, OR_ROLE_SUMSQ_EZ, 0, 0, 0); /* :116 */
   sc *e_r = (sc *)malloc(sizeof(sc) * (size_t)n), *e_x = (sc *)malloc(sizeof(sc) * (size_t)n);
   for (int i = 0; i < n; i++) { /* :119-139 */
     or_t_append_element(&t, "R_x", &cts[i].R);
     or_t_append_element(&t, "X", &cts[i].B);
-    or_rng_scalar(rng, &e_r[i]);
+    draw(rng, &e_r[i], OR_ROLE_SUMSQ_ER, 0, i, 0);
     ge c0, c1, c2;
     or_ge_mul_generator(&c0, &e_r[i]);
     or_t_append_element(&t, "[e_r]G", &c0);
-    or_rng_scalar(rng, &e_x[i]);
+    draw(rng, &e_x[i], OR_ROLE_SUMSQ_EX, 0, i, 0);
     or_ge_mul_generator(&c1, &e_x[i]);
     mul_k(&c2, pk, &e_r[i]);
     or_ge_add(&c1, &c1, &c2);
@@ -402,12 +455,12 @@ void or_sumsq_snapshot(const or_pubkey *pk, int n, const uint64_t *values, chach
   ge vg;
   or_sc_from_u64(&v, ss);
   or_ge_mul_generator(&vg, &v);
-  ext_ct_new(&sum_ct, &vg, pk, rng);
+  ext_ct_new(&sum_ct, &vg, pk, rng, OR_ROLE_VALUE_R, 0, 0);
   put_ct(out_cts, &sum_ct.R, &sum_ct.B);
   for (int i = 0; i < n; i++) {
     or_sc_from_u64(&v, values[i]);
     or_ge_mul_generator(&vg, &v);
-    ext_ct_new(&cts[i], &vg, pk, rng);
+    ext_ct_new(&cts[i], &vg, pk, rng, OR_ROLE_CT_R, 0, i);
     put_ct(out_cts + 64 * (size_t)(i + 1), &cts[i].R, &cts[i].B);
   }
   sumsq_new(pk, n, cts, values, &sum_ct, "test", rng, out_proof);
@@ -426,10 +479,10 @@ void or_qv_new(const or_qv_params *p, const uint64_t *votes, chacha_rng *rng, ui
   for (int i = 0; i < n; i++) credit += votes[i] * votes[i];
   for (int i = 0; i < n; i++)
     range_new(&p->pk, &p->vote_range, votes[i], "quadratic_voting_variant", rng,
-              out + (size_t)i * vote_sz, &cts[i]);
+              out + (size_t)i * vote_sz, &cts[i], i);
   ext_ct credit_ct;
   range_new(&p->pk, &p->credit_range, credit, "quadratic_voting_credit_range", rng,
-            out + (size_t)n * vote_sz, &credit_ct);
+            out + (size_t)n * vote_sz, &credit_ct, n);
   sumsq_new(&p->pk, n, cts, votes, &credit_ct, "quadratic_voting_credit_equiv", rng,
             out + (size_t)n * vote_sz + credit_sz);
   free(cts);
@@ -459,7 +512,7 @@ int or_decryption_share_new(const uint8_t sk_share[32], const uint8_t ct_random[
   or_ristretto_encode(out, &dh);
   merlin_t t;
   share_transcript(&t, shares, threshold, shared_key, index);
-  logeq_new(&base, (const sc *)sk_share, &ks, &dh, &t, rng, (sc *)(out + 32), (sc *)(out + 64));
+  logeq_new(&base, (const sc *)sk_share, &ks, &dh, &t, rng, (sc *)(out + 32), (sc *)(out + 64), 0);
   return 0;
 }
 
