@@ -161,7 +161,8 @@ int eg_mul_generator_batch(eg_ctx*, size_t n, const uint8_t* k /*32n*/, uint8_t*
 int eg_vartime_double_mul_generator_batch(eg_ctx*, size_t n, const uint8_t* k, const uint8_t* p, const uint8_t* r,
                                           uint8_t* out, uint8_t* ok);
 /* Group::vartime_multi_mul(scalars, elements) (ristretto.rs:139-145): n problems of `terms` terms each,
- * scalars/points laid out [problem][term][32] */
+ * scalars/points laid out [problem][term][32].  Scalars must be canonical (< l), as in the reference; this holds for every
+ * multi-scalar entry below too (the Straus path is only correct below 2^253). */
 int eg_vartime_multi_mul_batch(eg_ctx*, size_t n, size_t terms, const uint8_t* scalars, const uint8_t* points,
                                uint8_t* out, uint8_t* ok);
 /* The same multi-scalar multiplication on DEVICE buffers, asynchronous on `stream`: out_i = enc( sum_t [k_it]P_it + [r_i]G ).
