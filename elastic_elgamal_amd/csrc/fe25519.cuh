@@ -16,9 +16,13 @@
 // Limb i sits at bit POS(i) = ceil(85 i / 3): 0 29 57 85 114 142 170 199 227.  A product of limbs i and j lands on limb i + j times
 // 2^e, e = 1 when (i mod 3, j mod 3) is (1,1), (1,2) or (2,1) and 0 otherwise (fe_mul doubles limb i of the first operand there).
 //
-// Bound discipline.  "class c" means limb i <= c * 2^W(i) (limb 1 a hair above for c = 1).
-//   fe_mul(h, f, g): needs class(f) * class(g) <= 12.5 (column sums < 2^64) and both classes < 7.9; output class 1.
-//   fe_sq(h, f):     needs class(f) <= 3.5; output class 1.
+// Bound discipline.  "class c" means limb i <= c * 2^W(i) (limb 1 a hair above for c = 1: the final wrap of fe_mul / fe_sq adds
+// (limb 0 + 19 * carry) >> 29 <= 2432 to it, 2142 at the worst admitted input; fe_carry adds at most 1).
+//   fe_mul(h, f, g): needs class(f) * class(g) <= 12.5 (column sums < 2^64) and both classes <= 7.9; output class 1.
+//                    With every limb at the top of its class the largest column sum is 0.078125 * class(f) * class(g) * 2^64:
+//                    0.9766 * 2^64 at 12.5 (0.9785 with the 0.1 % + 4096 that fe_check_values tolerates), 2^64 at 12.8; the final
+//                    carry stays below 2^36.  Pinned by tests/limb_cases.py (column model, corner cases) on the host and on the GPU.
+//   fe_sq(h, f):     needs class(f) <= 3.5 (largest column sum 0.957 * 2^64); output class 1.
 //   fe_add:          class(f) + class(g) <= 7.9.     fe_sub: class(f) + 2 (g must be class 1).
 //   fe_sub4:         class(f) + 4 (g < class 4).     fe_carry: any class <= 7.9 -> class 1.
 // Compiled with -DEG_BOUNDCHECK on the host (tests/hostcheck) every fe carries its class and each

@@ -8,6 +8,7 @@
 #include "../../elastic_elgamal_amd/csrc/ge25519.cuh"
 #include "../../elastic_elgamal_amd/csrc/sc25519.cuh"
 #include "../../elastic_elgamal_amd/csrc/merlin.cuh"
+#include "../devcheck/limb_ops.cuh"
 
 using namespace eg;
 
@@ -406,3 +407,25 @@ extern "C" int hc_sum_table_grouped(int n, int group, const uint8_t* ps, const u
 extern "C" int hc_sum_table_mul(int n, const uint8_t* ps, const uint8_t k[32], const uint8_t r[32], uint8_t out[32]) { return g_teeth == 5 ? hc_sum_table_mul_t<5>(n, ps, k, r, out) : g_teeth == 7 ? hc_sum_table_mul_t<7>(n, ps, k, r, out) : hc_sum_table_mul_t<6>(n, ps, k, r, out); }
 extern "C" int hc_double_mul_generator_halved(const uint8_t k[32], const uint8_t p_enc[32], const uint8_t r[32], uint8_t out[32]) { return g_teeth == 5 ? hc_double_mul_generator_halved_t<5>(k, p_enc, r, out) : g_teeth == 7 ? hc_double_mul_generator_halved_t<7>(k, p_enc, r, out) : hc_double_mul_generator_halved_t<6>(k, p_enc, r, out); }
 extern "C" void hc_op_counts(unsigned long long out[28]) { if (g_teeth == 5) hc_op_counts_t<5>(out); else if (g_teeth == 7) hc_op_counts_t<7>(out); else hc_op_counts_t<6>(out); }
+
+// ---- raw-limb entries (tests/limb_cases.py, tests/test_limb_corners_cpu.py) ----------------------------------------------------------
+// n cases of one operation of tests/devcheck/limb_ops.cuh: in = n x LIMB_WORDS words, cls = n x LIMB_SLOTS classes of the input
+// elements, out = n x LIMB_WORDS words (zeroed here).  The classes are asserted against the limbs and carried through the operation,
+// so a case outside the precondition of its operation ends in abort(), as everywhere in this build.
+extern "C" void hc_limb_ops(int op, int n, const uint32_t* in, const float* cls, uint32_t* out) {
+  memset(out, 0, sizeof(uint32_t) * LIMB_WORDS * (size_t)n);
+  for (int i = 0; i < n; ++i) {
+    const u32* ci = in + (size_t)LIMB_WORDS * i;
+    const float* cc = cls + (size_t)LIMB_SLOTS * i;
+    u32* co = out + (size_t)LIMB_WORDS * i;
+    switch (limb_op_group(op)) {
+      case 0: limb_field_op(op, ci, cc, co); break;
+      case 1: limb_canon_op(op, ci, cc, co); break;
+      case 2: limb_chain_op(op, ci, cc, co); break;
+      case 3: limb_p1p1_op(op, ci, cc, co); break;
+      case 4: limb_point_op(op, ci, cc, co); break;
+      default: limb_scalar_op(op, ci, co); break;
+    }
+  }
+}
+extern "C" int hc_limb_op_count() { return LOP_COUNT; }

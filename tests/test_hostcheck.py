@@ -17,7 +17,7 @@ P = 2**255 - 19
 @pytest.fixture(scope="module")
 def hc():
     lib = HERE / "libhostcheck.so"
-    srcs = [HERE / "hostcheck.cpp"] + list((HERE.parent.parent / "elastic_elgamal_amd" / "csrc").glob("*.cuh"))
+    srcs = [HERE / "hostcheck.cpp", HERE.parent / "devcheck" / "limb_ops.cuh"] + list((HERE.parent.parent / "elastic_elgamal_amd" / "csrc").glob("*.cuh"))
     if not lib.exists() or any(s.stat().st_mtime > lib.stat().st_mtime for s in srcs):
         subprocess.check_call(
             ["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-DEG_BOUNDCHECK", "-fsanitize=undefined",
@@ -49,7 +49,7 @@ def test_field_ops(hc):
         hc.hc_fe_roundtrip(a.to_bytes(32, "little"), out)
         assert int.from_bytes(out.raw, "little") == a % P
     for a in vals:
-        for b in vals[:14]:
+        for b in (vals[:14] if a not in edge else vals):       # every edge value in both positions
             out = _b(160)
             hc.hc_fe_ops(a.to_bytes(32, "little"), b.to_bytes(32, "little"), out)
             r = [int.from_bytes(out.raw[32 * i : 32 * i + 32], "little") for i in range(5)]
