@@ -185,6 +185,9 @@ def _load() -> C.CDLL:
         "eg_qv_encrypt_votes_batch": (C.c_int, [vp, C.c_uint64, sz, sz, C.c_uint64, vp, cp]),
         "eg_qv_encrypt_votes_batch_device": (C.c_int, [vp, C.c_uint64, sz, sz, C.c_uint64, vp, vp, vp]),
         "eg_sumsq_params_create": (C.c_int, [vp, cp, C.c_int, cp, sz, C.POINTER(vp)]),
+        "eg_commit_equiv_params_create": (C.c_int, [vp, cp, cp, cp, sz, C.POINTER(vp)]),
+        "eg_commit_equiv_prove_batch": (C.c_int, [vp, C.c_uint64, sz, sz, C.c_uint64, vp, vp, vp]),
+        "eg_commit_equiv_prove_batch_device": (C.c_int, [vp, C.c_uint64, sz, sz, C.c_uint64, vp, vp, vp, vp]),
         "eg_merlin_challenge_batch": (C.c_int, [vp, sz, cp, sz, cp, sz, cp, sz, cp, sz, cp, sz]),
         "eg_choice_pack_json": (C.c_int, [C.c_int, C.c_int, cp, sz, C.c_int, sz, vp, vp, C.POINTER(sz)]),
         "eg_qv_pack_json": (C.c_int, [C.c_int, C.c_uint64, cp, sz, C.c_int, sz, vp, vp, C.POINTER(sz)]),
@@ -224,7 +227,7 @@ def _load() -> C.CDLL:
 
 
 PACK_RESHAPE = 0xFFFFFFFE
-ABI_VERSION = 6          # include/eg_hip.h: EG_ABI_VERSION
+ABI_VERSION = 7          # include/eg_hip.h: EG_ABI_VERSION
 
 
 def pack_json(text, n_options: int, single: bool | None = None, credits: int | None = None, threads: int = 0, max_objects: int = 0):
@@ -301,7 +304,7 @@ def plan_describe(kind: str, n_options: int = 0, credits_or_bound: int = 0) -> d
     """Summary of the flattened verification plan (host logic only, no GPU needed)."""
     import json
 
-    kinds = {"single": 0, "multi": 1, "qv": 2, "zero": 3, "bool": 4, "range": 5, "sumsq": 6}
+    kinds = {"single": 0, "multi": 1, "qv": 2, "zero": 3, "bool": 4, "range": 5, "sumsq": 6, "commit_equiv": 7}
     b = C.create_string_buffer(4096)
     _check(_load().eg_plan_describe(kinds[kind], n_options, credits_or_bound, b, 4096))
     return json.loads(b.value.decode())
@@ -878,6 +881,10 @@ class PublicKeyVerifier:
         _check(_load().eg_verify_proof_batch(self._h, n, buf, st))
         return list(st[:n])
 
+    def verify_device(self, n: int, d_items: int, d_status: int, stream: int = 0):
+        """n items at device pointer d_items -> n status words (uint32) at d_status; asynchronous on `stream`."""
+        _check(_load().eg_verify_proof_batch_device(self._h, n, d_items, d_status, stream))
+
     def close(self):
         if getattr(self, "_h", None):
             _load().eg_proof_params_destroy(self._h)
@@ -899,6 +906,48 @@ class SumOfSquaresVerifier(PublicKeyVerifier):
         self._h = C.c_void_p()
         _check(_load().eg_sumsq_params_create(ctx._h, public_key, n_values, label, len(label), C.byref(self._h)))
         self.item_size = _load().eg_proof_item_size(self._h)
+
+
+class CommitmentEquivalenceVerifier(PublicKeyVerifier):
+    """Batched ``CommitmentEquivalenceProof::verify`` (src/proofs/commitment.rs:186-238) with ``Transcript::new(label)``: the ElGamal
+    ciphertext (R, B) under `public_key` and the Pedersen commitment C = [v]G + [r_c]H over `blinding_base` H hide the same value.
+    item (224 bytes) = R || B || C || challenge || randomness_response || value_response || commitment_response
+    (serde.pack_commitment_equivalence packs the reference's object).  H must not be the identity."""
+
+    ITEM_SIZE = 224
+
+    def __init__(self, ctx: Context, public_key: bytes, blinding_base: bytes, label: bytes):
+        self.ctx, self.kind = ctx, 5
+        self.public_key, self.blinding_base, self.label = public_key, blinding_base, label
+        if len(public_key) != 32 or len(blinding_base) != 32:
+            raise ValueError("public_key and blinding_base are 32-byte encodings")
+        self._h = C.c_void_p()
+        _check(_load().eg_commit_equiv_params_create(ctx._h, public_key, blinding_base, label, len(label), C.byref(self._h)))
+        self.item_size = _load().eg_proof_item_size(self._h)
+
+    def verify(self, items: bytes):
+        """Status words of the packed items (host memory)."""
+        return self.verify_batch(items)
+
+    def prove(self, base_seed: int, first: int, values, rng_skip: int = 0, with_blindings: bool = False):
+        """``CommitmentEquivalenceProof::new`` on the GPU, one item per value (test and benchmark inputs: variable time); item i draws
+        from ChaChaRng::seed_from_u64(base_seed + first + i) after `rng_skip` 64-byte draws.  Returns the packed items, and the blinding
+        scalars r_c (32 bytes each) as well when `with_blindings`."""
+        vals = [int(v) for v in values]
+        n = len(vals)
+        arr = (C.c_uint64 * max(n, 1))(*vals)
+        out = C.create_string_buffer(max(n * self.item_size, 1))
+        bl = C.create_string_buffer(max(n * 32, 1)) if with_blindings else None
+        _check(_load().eg_commit_equiv_prove_batch(self._h, base_seed, first, n, rng_skip, arr, out, bl))
+        items = out.raw[: n * self.item_size]
+        return (items, bl.raw[: n * 32]) if with_blindings else items
+
+    def prove_device(self, base_seed: int, first: int, n: int, d_values: int, d_items: int, d_blindings: int = 0, rng_skip: int = 0,
+                     stream: int = 0):
+        """The same on device buffers: n uint64 values at d_values -> n items at d_items (and n x 32 bytes of r_c at d_blindings
+        unless 0); asynchronous on `stream`."""
+        _check(_load().eg_commit_equiv_prove_batch_device(self._h, base_seed, first, n, rng_skip, d_values, d_items,
+                                                          d_blindings or None, stream))
 
 
 class DecryptionShareVerifier(PublicKeyVerifier):

@@ -20,3 +20,8 @@ void eg_launch_qv_encrypt(int blocks, hipStream_t s, u64 seed0, size_t n, int n_
   hipLaunchKernelGGL(k_qv_encrypt, dim3(blocks), dim3(NT), 0, s, seed0, n, n_options, credits, votes, rng_skip, v, c, pre_sumsq, tabG, tabK,
                      prefixes, out, stride_words, vote_words, credit_words, gws);
 }
+
+void eg_launch_commit_equiv_prove(int blocks, hipStream_t s, u64 seed0, size_t n, u64 rng_skip, const u64* values, const uint4* tabG,
+                                  const uint4* tabK, const uint4* tabH, const u32* prefixes, int pre, u32* out, u32* blindings) {
+  hipLaunchKernelGGL(k_commit_equiv_prove, dim3(blocks), dim3(NT), 0, s, seed0, n, rng_skip, values, tabG, tabK, tabH, prefixes, pre, out, blindings);
+}

@@ -39,6 +39,8 @@ void eg_launch_qv_encrypt(int blocks, hipStream_t s, u64 seed0, size_t n, int n_
 void eg_launch_choice_encrypt(int blocks, hipStream_t s, u64 seed0, size_t n, int n_options, int single, int n_selected,
                               const u32* selection, u64 rng_skip, const uint4* tabG, const uint4* tabK, const u32* prefixes, int pre_main, int pre_ring,
                               int pre_logeq, u32* out, u32 stride_words, u32* gws);
+void eg_launch_commit_equiv_prove(int blocks, hipStream_t s, u64 seed0, size_t n, u64 rng_skip, const u64* values, const uint4* tabG,
+                                  const uint4* tabK, const uint4* tabH, const u32* prefixes, int pre, u32* out, u32* blindings);
 unsigned eg_gen_choice_ws_words(int n_options);
 unsigned eg_gen_qv_ws_words(int n_options, unsigned max_rings, unsigned max_responses);
 
@@ -254,7 +256,10 @@ struct Engine {
   unsigned char* d_blob = nullptr;
   uint4 *d_tabK = nullptr, *d_cpts = nullptr;   // d_tabK: comb table of the election key (first entry; see comb_table_build)
   uint4* d_tabK_big = nullptr;                 // its wide form, built with the context's (ensure_big_tables)
-  bool use_big = false;                        // this call reads the wide tables
+  uint4 *d_tabH = nullptr, *d_tabH_big = nullptr;   // plans with a third fixed base H (Plan::h_srcs): its comb tables, as K's; else null
+  egplan::ScalarSrc* d_h_srcs = nullptr;       // Plan::h_srcs
+  u32* d_h_words = nullptr;                    // [PT_WORDS..2 PT_WORDS) H (k_setup_points writes the generator in front)
+  bool use_big = false;                        // this call reads the wide tables (one launch, one width: all of G, K and H, or none)
   size_t items_seen = 0;                       // items verified by this engine so far (the wide tables are built once it passes ctx->big_min)
   u32* d_prefixes = nullptr;
   u32* d_key_words = nullptr;   // [0..PT_WORDS) generator, [PT_WORDS..2 PT_WORDS) key
@@ -338,7 +343,7 @@ static void engine_free(Engine* e) {
   if (!e) return;
   void* ptrs[] = {e->d_pt_items, e->d_sc_items, e->d_dclasses, e->d_dterms, e->d_jobs, e->d_vterms, e->d_insts, e->d_ops,
                   e->d_rules, e->d_tally_slots, e->d_base_slots, e->d_sum_bases, e->d_sum_members, e->d_acc_sums, e->d_acc_members, e->d_defer_slots, e->d_blob, e->d_cpts, e->d_prefixes, e->d_key_words,
-                  e->tally_saved, e->tally_saved2, e->tally_saved3, e->d_tally_enc, e->d_wire, e->d_status, e->gen_ws, e->d_gen_desc};
+                  e->tally_saved, e->tally_saved2, e->tally_saved3, e->d_tally_enc, e->d_wire, e->d_status, e->gen_ws, e->d_gen_desc, e->d_h_srcs, e->d_h_words};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   for (auto& w : e->set) {
     void* sp[] = {w.pts, w.cmp, w.chal, w.states, w.flags, w.bad_item, w.btab, w.dpt, w.sacc, w.encw, w.partial, w.tally};
@@ -350,6 +355,7 @@ static void engine_free(Engine* e) {
   if (e->last_done) (void)hipEventDestroy(e->last_done);
   if (e->saved_ev) (void)hipEventDestroy(e->saved_ev);
   comb_table_free(e->d_tabK); comb_table_free(e->d_tabK_big);
+  comb_table_free(e->d_tabH); comb_table_free(e->d_tabH_big);
   if (e->copy_stream) (void)hipStreamDestroy(e->copy_stream);
   if (e->json_ring) (void)hipHostFree(e->json_ring);
   if (e->json_status_ring) (void)hipHostFree(e->json_status_ring);
@@ -373,6 +379,7 @@ static EngineBufs make_bufs(const Engine* e, int set, const void* d_ballots, u32
   B.sacc = w.sacc;
   B.dpt = w.dpt;
   B.encw = w.encw;
+  B.tabH = e->use_big ? e->d_tabH_big : e->d_tabH;
   return B;
 }
 
@@ -438,7 +445,8 @@ static int grid_for(size_t lanes, int cap_blocks) {
 }
 
 // build device state for a plan + election key
-static int engine_create(eg_ctx* ctx, eghost::Plan&& plan, const uint8_t pk[32], int n_options, Engine** out) {
+// h: encoding of the third fixed base of a plan with H terms (Plan::h_srcs), null for every other plan
+static int engine_create(eg_ctx* ctx, eghost::Plan&& plan, const uint8_t pk[32], int n_options, Engine** out, const uint8_t* h = nullptr) {
   std::unique_ptr<Engine, void (*)(Engine*)> e(new Engine(), engine_free);
   e->ctx = ctx;
   e->plan = std::move(plan);
@@ -483,6 +491,8 @@ static int engine_create(eg_ctx* ctx, eghost::Plan&& plan, const uint8_t pk[32],
   e->n_sums = (int)F.sums.size();
   if ((rc = upload(&e->d_defer_slots, defer_slots, s))) return rc;
   if ((rc = upload(&e->d_blob, P.blob, s))) return rc;
+  if (P.has_h() != (h != nullptr)) return fail(EG_ERR_BAD_ARG, "internal: a plan has terms over a third fixed base exactly when one is given");
+  if (P.has_h() && (rc = upload(&e->d_h_srcs, P.h_srcs, s))) return rc;
 
   // election key: decode, reject invalid / identity (keys/mod.rs:161-176), fixed-base table
   u32* d_pk = nullptr;
@@ -499,6 +509,19 @@ static int engine_create(eg_ctx* ctx, eghost::Plan&& plan, const uint8_t pk[32],
   if (!hflags[0]) return fail(EG_ERR_BAD_PUBLIC_KEY, "public key is not a valid ristretto255 encoding");
   if (hflags[1]) return fail(EG_ERR_BAD_PUBLIC_KEY, "public key is the identity");
   if ((rc = comb_table_build(e->d_key_words + PT_WORDS, EG_COMB_BITS, s, &e->d_tabK))) return rc;
+  if (h) {   // the third fixed base: decoded like the key; the identity is refused (its comb table is a case nothing here has ever built)
+    HIPCHK(hipMalloc((void**)&d_pk, 32));
+    HIPCHK(hipMalloc((void**)&d_flags, 8));
+    HIPCHK(hipMalloc((void**)&e->d_h_words, 2 * PT_WORDS * sizeof(u32)));
+    HIPCHK(hipMemcpyAsync(d_pk, h, 32, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_setup_points, dim3(1), dim3(64), 0, s, d_pk, e->d_h_words, d_flags);
+    HIPCHK(hipMemcpyAsync(hflags, d_flags, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    (void)hipFree(d_pk); (void)hipFree(d_flags);
+    if (!hflags[0]) return fail(EG_ERR_BAD_ARG, "blinding base is not a valid ristretto255 encoding");
+    if (hflags[1]) return fail(EG_ERR_BAD_ARG, "blinding base is the identity");
+    if ((rc = comb_table_build(e->d_h_words + PT_WORDS, EG_COMB_BITS, s, &e->d_tabH))) return rc;
+  }
 
   // election-constant points [m]G
   {
@@ -589,7 +612,16 @@ static int ensure_big_tables(Engine* e, hipStream_t s) {
     if (rc == EG_ERR_NOMEM) { ctx->big_failed = true; return EG_OK; }
     if (rc) return rc;
   }
+  if (e->d_tabH && !e->d_tabH_big) {     // a third base goes wide with the other two, or all three stay narrow (engine_wide)
+    const int rc = comb_table_build(e->d_h_words + PT_WORDS, ctx->big_bits, s, &e->d_tabH_big, true);
+    if (rc == EG_ERR_NOMEM) { ctx->big_failed = true; return EG_OK; }
+    if (rc) return rc;
+  }
   return EG_OK;
+}
+// one launch reads one width: the wide tables only when every fixed base of the engine has one
+static bool engine_wide(const Engine* e) {
+  return e->d_tabK_big != nullptr && e->ctx->tabG_big != nullptr && (e->d_tabH == nullptr || e->d_tabH_big != nullptr);
 }
 
 // the kernels that touch the per-ballot comb tables exist once per comb shape (template parameter T, ge25519.cuh: Teeth<T>)
@@ -617,7 +649,7 @@ static int engine_verify_device(Engine* e, size_t n, const void* d_ballots, void
   int rc;
   e->items_seen += n;
   if (e->items_seen >= ctx->big_min && (rc = ensure_big_tables(e, s))) return rc;
-  e->use_big = e->d_tabK_big != nullptr && ctx->tabG_big != nullptr;
+  e->use_big = engine_wide(e);
   if ((rc = prof_begin(ctx, s, PROF_CALL, &all_idx))) return rc;
   // equal-sized chunks (each a multiple of the block size) so that the persistent grids stay balanced on the last chunk; with two
   // work sets a batch that is worth splitting gets an even number of chunks, so that both streams carry the same load
@@ -727,7 +759,10 @@ static int engine_verify_device(Engine* e, size_t n, const void* d_ballots, void
                                                    (size_t)group * 9 * NT * sizeof(u32), cs, B, e->d_jobs, e->d_vterms, st.fam_first[FAM_TABLEN],
                                                    st.fam_count[FAM_TABLEN], group));
       }
-      if (st.fam_count[FAM_DIRECT1])
+      if (st.fam_count[FAM_DIRECT1] && e->d_tabH)       // a plan with a third fixed base: the kernel that also reads the table of H
+        hipLaunchKernelGGL(k_eq_direct_h, dim3(grid_for((size_t)st.fam_count[FAM_DIRECT1] * cn, msm_blocks)), dim3(NT), 0, cs, B,
+                           e->d_jobs, e->d_vterms, e->d_h_srcs, st.fam_first[FAM_DIRECT1], st.fam_count[FAM_DIRECT1]);
+      else if (st.fam_count[FAM_DIRECT1])
         hipLaunchKernelGGL(k_eq_direct, dim3(grid_for((size_t)st.fam_count[FAM_DIRECT1] * cn, msm_blocks)), dim3(NT), 0, cs, B,
                            e->d_jobs, e->d_vterms, st.fam_first[FAM_DIRECT1], st.fam_count[FAM_DIRECT1]);
       if (st.fam_count[FAM_GENERIC])
@@ -1619,7 +1654,7 @@ static int prepare_wide(Engine* e) {
   HIPCHK(hipDeviceSynchronize());
   const int rc = ensure_big_tables(e, e->ctx->stream);
   if (rc) return rc;
-  if (e->ctx->big_bits && (!e->ctx->tabG_big || !e->d_tabK_big)) return fail(EG_ERR_NOMEM, "the wide comb tables do not fit the device memory");
+  if (e->ctx->big_bits && !engine_wide(e)) return fail(EG_ERR_NOMEM, "the wide comb tables do not fit the device memory");
   return EG_OK;
 }
 int eg_choice_prepare_wide_tables(eg_choice_params* p) { EG_LOCK_P(p); return p ? prepare_wide(p->eng) : fail(EG_ERR_BAD_ARG, "null"); }
@@ -1985,6 +2020,15 @@ int eg_sumsq_params_create(eg_ctx* c, const uint8_t pk[32], int n_values, const 
   *out = new eg_proof_params{e, EG_PROOF_SUMSQ, item};
   return EG_OK;
 }
+int eg_commit_equiv_params_create(eg_ctx* c, const uint8_t pk[32], const uint8_t blinding_base[32], const char* label, size_t label_len,
+                                  eg_proof_params** out) { EG_LOCK(c);
+  if (!c || !pk || !blinding_base || !out || (!label && label_len)) return fail(EG_ERR_BAD_ARG, "bad argument");
+  if (label_len > 255) return fail(EG_ERR_BAD_ARG, "label up to 255 bytes");
+  Engine* e = nullptr;
+  TRY(engine_create(c, eghost::build_commit_equiv_plan(std::string(label ? label : "", label_len)), pk, 0, &e, blinding_base));
+  *out = new eg_proof_params{e, EG_PROOF_COMMIT_EQUIV, eghost::COMMIT_EQUIV_ITEM};
+  return EG_OK;
+}
 void eg_proof_params_destroy(eg_proof_params* p) { params_destroy(p); }
 size_t eg_proof_item_size(const eg_proof_params* p) { return p ? p->item_size : 0; }
 int eg_verify_proof_batch(eg_proof_params* p, size_t n, const uint8_t* items, uint32_t* status) { EG_LOCK_P(p);
@@ -2017,6 +2061,7 @@ int eg_plan_describe(int kind, int n_options, uint64_t credits_or_bound, char* b
     case 4: P = eghost::build_bool_plan(); break;
     case 5: P = eghost::build_range_plan(credits_or_bound, &item); break;
     case 6: P = eghost::build_sumsq_plan(n_options, "test", &item); break;
+    case 7: P = eghost::build_commit_equiv_plan("test"); break;
     default: return fail(EG_ERR_BAD_ARG, "unknown plan kind");
   }
   size_t jobs = 0, insts = 0, var_terms = P.vterms.size(), table_terms = 0, derived = 0;
@@ -2027,7 +2072,7 @@ int eg_plan_describe(int kind, int n_options, uint64_t credits_or_bound, char* b
     jobs += st.jobs.size(); insts += st.insts.size();
     per_stage += (per_stage.empty() ? "" : ",") + std::to_string(st.jobs.size());
     for (auto& j : st.jobs) {
-      combs += (j.g.kind != egplan::SRC_NONE) + (j.k.kind != egplan::SRC_NONE);
+      combs += (j.g.kind != egplan::SRC_NONE) + (j.k.kind != egplan::SRC_NONE) + (j.h != 0);
       if (j.defer) ++deferred; else ++plain_encodes;
       switch (job_family(j, P.vterms)) {
         case FAM_TABLE1: ++jobs_table1; break;
@@ -2992,6 +3037,39 @@ int eg_qv_encrypt_votes_batch(eg_qv_params* p, uint64_t base_seed, size_t first,
   TRY(vv.put(votes, n * (size_t)p->n_options * 4, e->ctx->stream));
   TRY(qv_encrypt_device(p, base_seed, first, n, vv.p, rng_skip, d.p, e->ctx->stream));
   TRY(d.get(out, n * e->plan.stride, e->ctx->stream));
+  HIPCHK(hipStreamSynchronize(e->ctx->stream));
+  return EG_OK;
+}
+
+// CommitmentEquivalenceProof::new per item (prover_kernels.cuh: k_commit_equiv_prove), over the narrow comb tables of G, K and H
+static int commit_equiv_prove_device(eg_proof_params* p, uint64_t base_seed, size_t first, size_t n, uint64_t rng_skip, const void* d_values,
+                                     void* d_items, void* d_blindings, hipStream_t s) {
+  Engine* e = p->eng;
+  if (p->kind != EG_PROOF_COMMIT_EQUIV || !e->d_tabH) return fail(EG_ERR_BAD_ARG, "not a commitment-equivalence params object");
+  HIPCHK(hipSetDevice(e->ctx->device));
+  if (n == 0) return EG_OK;
+  eg_launch_commit_equiv_prove(grid_for(n, e->ctx->cus * 4), s, base_seed + first, n, rng_skip, reinterpret_cast<const u64*>(d_values),
+                               e->ctx->tabG, e->d_tabK, e->d_tabH, e->d_prefixes, e->plan.gen_pre_cequiv, reinterpret_cast<u32*>(d_items),
+                               reinterpret_cast<u32*>(d_blindings));
+  HIPCHK(hipGetLastError());
+  return EG_OK;
+}
+int eg_commit_equiv_prove_batch_device(eg_proof_params* p, uint64_t base_seed, size_t first, size_t n, uint64_t rng_skip, const void* d_values,
+                                       void* d_items, void* d_blindings, void* stream) { EG_LOCK_P(p);
+  if (!p || (n && (!d_values || !d_items))) return fail(EG_ERR_BAD_ARG, "bad argument");
+  return commit_equiv_prove_device(p, base_seed, first, n, rng_skip, d_values, d_items, d_blindings, (hipStream_t)stream);
+}
+int eg_commit_equiv_prove_batch(eg_proof_params* p, uint64_t base_seed, size_t first, size_t n, uint64_t rng_skip, const uint64_t* values,
+                                uint8_t* items, uint8_t* blindings) { EG_LOCK_P(p);
+  if (!p || (n && (!values || !items))) return fail(EG_ERR_BAD_ARG, "bad argument");
+  Engine* e = p->eng;
+  HIPCHK(hipSetDevice(e->ctx->device));
+  DevBuf v, d, b;
+  TRY(v.alloc(n * 8)); TRY(d.alloc(n * eghost::COMMIT_EQUIV_ITEM)); TRY(b.alloc(n * 32));
+  TRY(v.put(values, n * 8, e->ctx->stream));
+  TRY(commit_equiv_prove_device(p, base_seed, first, n, rng_skip, v.p, d.p, blindings ? b.p : nullptr, e->ctx->stream));
+  TRY(d.get(items, n * eghost::COMMIT_EQUIV_ITEM, e->ctx->stream));
+  if (blindings) TRY(b.get(blindings, n * 32, e->ctx->stream));
   HIPCHK(hipStreamSynchronize(e->ctx->stream));
   return EG_OK;
 }

@@ -104,6 +104,11 @@ struct Plan {
   std::vector<uint32_t> tally_slots;
   std::vector<uint8_t> blob;
   std::vector<uint64_t> const_mults;          // election-constant points [m]G
+  // scalar sources of the terms over the THIRD fixed base H (the blinding base of a Pedersen commitment, commitment.rs:222-229): a side
+  // array that JobClass::h indexes, so that the job classes the ballot kernels read keep their layout.  Only equations of FAM_DIRECT1
+  // may carry one (k_eq_direct_h is the one kernel that reads the table of H); empty for every plan without such a base.
+  std::vector<ScalarSrc> h_srcs;
+  bool has_h() const { return !h_srcs.empty(); }
   std::vector<std::vector<HashOp>> prefix_programs;
   int n_pt_slots = 0, n_cmp_slots = 0, n_chal_slots = 0, n_state_slots = 0, n_flag_slots = 0, n_prefixes = 0;
   std::map<std::string, uint32_t> blob_index;
@@ -182,7 +187,7 @@ struct Plan {
   }
   int pk_off = -1;
   int gen_pre_main = -1, gen_pre_ring = -1, gen_pre_logeq = -1;  // prefix indices used by the ballot generator
-  int gen_vote_main = -1, gen_vote_ring = -1, gen_credit_main = -1, gen_credit_ring = -1, gen_pre_sumsq = -1;
+  int gen_vote_main = -1, gen_vote_ring = -1, gen_credit_main = -1, gen_credit_ring = -1, gen_pre_sumsq = -1, gen_pre_cequiv = -1;
   uint32_t pk_ref() {  // 32 bytes of the election key; filled in when the params object is created
     if (pk_off < 0) { pk_off = (int)blob.size(); blob.insert(blob.end(), 32, 0); }
     return blob_ref((uint32_t)pk_off, 32);
@@ -218,14 +223,15 @@ struct Plan {
     return dc.out_slot;
   }
   // out = encode(sum terms + [g]G + [k]K); returns the compressed slot
-  uint16_t job(size_t st, const std::vector<VarTerm>& terms, ScalarSrc g, ScalarSrc k) {
+  uint16_t job(size_t st, const std::vector<VarTerm>& terms, ScalarSrc g, ScalarSrc k, ScalarSrc h = ScalarSrc{SRC_NONE, 0, 0, 0}) {
     JobClass jc;
     jc.term_first = (uint16_t)vterms.size();
     jc.term_count = (uint16_t)terms.size();
     jc.g = g; jc.k = k;
     jc.out_slot = new_cmp();
     jc.enc_slot = 0xffff;
-    jc.defer = 1; jc.pad = 0;
+    jc.defer = 1; jc.h = 0;
+    if (h.kind != SRC_NONE) { h_srcs.push_back(h); jc.h = (uint16_t)h_srcs.size(); }
     vterms.insert(vterms.end(), terms.begin(), terms.end());
     stage(st).jobs.push_back(jc);
     stage(st).deferred.push_back(jc.out_slot);
@@ -237,7 +243,7 @@ struct Plan {
     jc.g = ScalarSrc{SRC_NONE, 0, 0, 0}; jc.k = ScalarSrc{SRC_NONE, 0, 0, 0};
     jc.out_slot = new_cmp();
     jc.enc_slot = pt_slot;
-    jc.defer = 0; jc.pad = 0;
+    jc.defer = 0; jc.h = 0;
     stage(st).jobs.push_back(jc);
     return jc.out_slot;
   }
@@ -660,6 +666,39 @@ inline Plan build_sumsq_plan(int n, const std::string& label, size_t* item_size)
   return P;
 }
 
+// ---- CommitmentEquivalenceProof::verify (commitment.rs:186-238) with transcript = Transcript::new(label) ---------------------------
+// item = R || B (Ciphertext::to_bytes) || C || challenge || randomness_response || value_response || commitment_response (224 B).
+//   [s_r]G - [c]R        [s_v]G + [s_r]K - [c]B        [s_v]G + [s_c]H - [c]C        H = the commitment's blinding base
+// Every variable base is multiplied once: three FAM_DIRECT1 equations, no per-item comb tables.  H is the engine's third fixed base.
+constexpr size_t COMMIT_EQUIV_ITEM = 224;
+inline Plan build_commit_equiv_plan(const std::string& label) {
+  Plan P;
+  P.stride = COMMIT_EQUIV_ITEM;
+  const uint16_t R = P.wire_point(0), B = P.wire_point(1), C = P.wire_point(2);
+  for (int i = 3; i < 7; ++i) P.wire_scalar((uint16_t)i);
+  const uint32_t pre = P.new_prefix();
+  P.gen_pre_cequiv = (int)pre;
+  P.prefix_programs.push_back({{OP_NEW, P.ref(label), 0, 0},
+                               {OP_APPEND_BLOB, P.ref("dom-sep"), P.ref("commitment_equivalence"), 0},
+                               {OP_APPEND_BLOB, P.ref("K"), P.pk_ref(), 0},
+                               {OP_SAVE_PREFIX, 0, pre, 0}});
+  const ScalarSrc c = wire_src(3, true), s_r = wire_src(4), s_v = wire_src(5), s_c = wire_src(6);
+  const uint16_t er = P.job(0, {P.term(R, c)}, s_r, no_src());               // commitment.rs:201-205
+  const uint16_t eb = P.job(0, {P.term(B, c)}, s_v, s_r);                    // :208-219
+  const uint16_t ec = P.job(0, {P.term(C, c)}, s_v, no_src(), s_c);          // :222-229
+  const uint16_t flag = P.new_flag();
+  P.stage(0).insts.push_back({{OP_LOAD_PREFIX, 0, pre, 0},
+                              {OP_APPEND_WIRE, P.ref("R"), 0, 1},
+                              {OP_APPEND_WIRE, P.ref("B"), 1, 1},
+                              {OP_APPEND_WIRE, P.ref("C"), 2, 1},
+                              {OP_APPEND_CMP, P.ref("[e_r]G"), er, 0xffff},
+                              {OP_APPEND_CMP, P.ref("[e_v]G + [e_r]K"), eb, 0xffff},
+                              {OP_APPEND_CMP, P.ref("[e_v]G + [e_c]H"), ec, 0xffff},
+                              {OP_CHALLENGE_CHECK, P.ref("c"), 3, flag}});
+  P.rules.push_back({flag, 4 /* EG_ST_SUM_CHALLENGE: the bare ChallengeMismatch, as for the zero-encryption proof */});
+  return P;
+}
+
 // ---- PublicKeySet::verify_share (sharing/key_set.rs:209-228): item = R(32) || dh(32) || challenge || response -------------
 // LogEqualityProof with log_base = the ciphertext's random element R (per item) and powers = (participant key, dh):
 //   X_G = [s]G - [c]KS   (KS = participant key: the engine's fixed base "K")      X_K = [s]R - [c]dh
@@ -919,6 +958,12 @@ inline std::string check_flat_plan(const Plan& P, const FlatPlan& F) {
         if ((int)j.out_slot >= P.n_cmp_slots) return "job output out of range";
         if (!j.defer && (int)j.enc_slot >= P.n_pt_slots) return "encode job source out of range";
         if (!scalar_ok(j.g) || !scalar_ok(j.k)) return "job scalar out of range";
+        if (j.h) {      // a term over the third fixed base: its scalar lives in the side array, and only k_eq_direct_h evaluates it
+          if ((size_t)j.h > P.h_srcs.size()) return "job H scalar source out of range";
+          const ScalarSrc& hs = P.h_srcs[j.h - 1];
+          if (hs.kind == SRC_NONE || !scalar_ok(hs)) return "job H scalar out of range";
+          if (f != FAM_DIRECT1) return "H term in an equation family that has no table of H";
+        }
         for (unsigned t = 0; t < j.term_count; ++t) {
           const VarTerm& v = P.vterms[j.term_first + t];
           if (!scalar_ok(v.s) || v.s.kind == SRC_NONE) return "term scalar out of range";

@@ -260,6 +260,37 @@ __global__ void __launch_bounds__(NT, 2) k_eq_direct(EngineBufs B, const egplan:
   }
 }
 
+// k_eq_direct for plans with a THIRD fixed base H (CommitmentEquivalenceProof::verify, commitment.rs:222-229: [s_v]G + [s_c]H - [c]C):
+// an equation whose class names an H scalar (JobClass::h -> h_srcs) adds one more comb product, over B.tabH.  A kernel of its own, launched
+// only by plans that have such a term, so that the equation kernels of the ballots keep their registers and launches.
+__global__ void __launch_bounds__(NT, 2) k_eq_direct_h(EngineBufs B, const egplan::JobClass* classes, const egplan::VarTerm* terms,
+                                                       const egplan::ScalarSrc* h_srcs, int class_first, int n_classes) {
+  const size_t total = (size_t)n_classes * B.n;
+  WsTable tab;
+  tab.init(B.ws);
+  for (size_t j = (size_t)blockIdx.x * NT + threadIdx.x; j < total; j += (size_t)gridDim.x * NT) {
+    const u32 c = class_first + (u32)(j / B.n), b = (u32)(j % B.n);
+    const egplan::JobClass jc = classes[c];
+    const egplan::VarTerm vt = terms[jc.term_first];
+    u32 s[8], dg[8];
+    load_scalar(s, B, b, vt.s, true);
+    sc_recode_radix16(dg, s);
+    ge p, acc;
+    load_pt(p, B.pts, B.cap, vt.slot, b);
+    ge_var_table_build(tab, p);
+    ge_var_mul(acc, tab, dg);
+    eq_fixed_terms(acc, B, b, jc);
+    if (jc.h) {
+      const FixedTable th(B.tabH);
+      u32 sh[8], dh[EG_COMB_WORDS];
+      load_scalar(sh, B, b, h_srcs[jc.h - 1], true);
+      sc_recode_comb(dh, sh);
+      ge_fixed_mul_add(acc, th, dh);
+    }
+    store_pt(B.dpt, B.cap, jc.out_slot, b, acc);
+  }
+}
+
 template <int T>
 __global__ void __launch_bounds__(NT, 2) k_eq_generic(EngineBufs B, const egplan::JobClass* classes,
                                                       const egplan::VarTerm* terms, int class_first, int n_classes) {

@@ -8,7 +8,7 @@
 //   * wire items      which 32-byte items of the packed ballot are points / scalars
 //   * derived points  sums / differences of decoded points and election constants
 //                     (sum of ciphertexts choice.rs:363; B - x_j ring.rs:338; ct - sum(partials) range.rs:572)
-//   * job classes     per stage: out = encode( sum_i [a_i]P_i + [g]G + [k]K )  -- every group-side equation
+//   * job classes     per stage: out = encode( sum_i [a_i]P_i + [g]G + [k]K [+ [h]H] )  -- every group-side equation
 //   * hash programs   per stage: Merlin transcript ops producing the next challenges / final verdict flags
 //   * status rules    flag -> error code, in the reference's order of checks
 // Stages exist because equation j+1 of a ring needs the challenge hashed from equation j (ring.rs:354-360).
@@ -46,7 +46,7 @@ struct JobClass {
   uint16_t out_slot;                // compressed-output slot
   uint16_t enc_slot;                // if term_count == 0 and no g/k: just encode this point slot
   uint16_t defer;                   // 1: evaluate with halved scalars and leave the point for k_encode_batch (out = encode(2P))
-  uint16_t pad;
+  uint16_t h;                       // 0: no term over the third fixed base H; else 1 + index of its scalar in the plan's h_srcs (k_eq_direct_h)
 };
 
 struct DeriveTerm {

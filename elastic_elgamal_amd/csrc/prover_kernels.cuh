@@ -582,4 +582,61 @@ __global__ void __launch_bounds__(NT) k_qv_encrypt(u64 seed0, size_t n, int n_op
   }
 }
 
+// ---- CommitmentEquivalenceProof::new (commitment.rs:134-181) for one (ciphertext, commitment) per lane ---------------------------------
+// Draws after rng_skip: r (CiphertextWithValue::new, encryption.rs), r_c (SecretKey::generate), e_r, e_v, e_c.  The prover knows every
+// discrete logarithm, so R = [r]G, B = [v]G + [r]K, C = [v]G + [r_c]H and the three commitments are fixed-base products over the comb
+// tables of G, K and H.  out: 224-byte items (R || B || C || c || s_r || s_v || s_c); blindings (may be null): r_c per item.
+__global__ void __launch_bounds__(NT) k_commit_equiv_prove(u64 seed0, size_t n, u64 rng_skip, const u64* values, const uint4* tabG,
+                                                           const uint4* tabK, const uint4* tabH, const u32* prefixes, int pre, u32* out,
+                                                           u32* blindings) {
+  __shared__ u32 lds[50 * NT];
+  const FixedTable tg(tabG), tk(tabK), th(tabH);
+  for (size_t i = (size_t)blockIdx.x * NT + threadIdx.x; i < n; i += (size_t)gridDim.x * NT) {
+    ChaChaRng rng;
+    chacha_seed_from_u64(rng, seed0 + i);
+    rng.counter = rng_skip;
+    u32 v[8], r[8], rc[8], er[8], ev[8], ec[8];
+    sc_from_u64(v, values[i]);
+    rng_scalar(rng, r);
+    rng_scalar(rng, rc);
+    rng_scalar(rng, er);
+    rng_scalar(rng, ev);
+    rng_scalar(rng, ec);
+    u32* ob = out + i * 56;
+    u32 enc[8];
+    Transcript<LdsState> t;
+    t.st.base = lds + threadIdx.x;
+    gen_import(t, prefixes + (size_t)pre * 52);
+    fixed2_encode(enc, tg, r, tk, nullptr);
+    gen_append32(t, "R", 1, enc);
+#pragma unroll
+    for (int w = 0; w < 8; ++w) ob[w] = enc[w];
+    fixed2_encode(enc, tg, v, tk, r);
+    gen_append32(t, "B", 1, enc);
+#pragma unroll
+    for (int w = 0; w < 8; ++w) ob[8 + w] = enc[w];
+    fixed2_encode(enc, tg, v, th, rc);
+    gen_append32(t, "C", 1, enc);
+#pragma unroll
+    for (int w = 0; w < 8; ++w) ob[16 + w] = enc[w];
+    fixed2_encode(enc, tg, er, tk, nullptr);
+    gen_append32(t, "[e_r]G", 6, enc);
+    fixed2_encode(enc, tg, ev, tk, er);
+    gen_append32(t, "[e_v]G + [e_r]K", 15, enc);
+    fixed2_encode(enc, tg, ev, th, ec);
+    gen_append32(t, "[e_v]G + [e_c]H", 15, enc);
+    u32 c[8], sr[8], sv[8], sc[8];
+    gen_challenge(t, c);
+    gen_muladd(sr, c, r, er);
+    gen_muladd(sv, c, v, ev);
+    gen_muladd(sc, c, rc, ec);
+#pragma unroll
+    for (int w = 0; w < 8; ++w) { ob[24 + w] = c[w]; ob[32 + w] = sr[w]; ob[40 + w] = sv[w]; ob[48 + w] = sc[w]; }
+    if (blindings) {
+#pragma unroll
+      for (int w = 0; w < 8; ++w) blindings[i * 8 + w] = rc[w];
+    }
+  }
+}
+
 }  // namespace eg

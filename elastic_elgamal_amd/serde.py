@@ -103,6 +103,17 @@ def pack_range_encryption(obj: dict) -> bytes:
     return _ct(obj["ciphertext"]) + _range_proof(obj["proof"])
 
 
+def pack_commitment_equivalence(obj: dict) -> bytes:
+    """{"ciphertext": .., "commitment": .., "proof": CommitmentEquivalenceProof} as produced by tests/snapshots.rs:163-190
+    (examples/equivalence.rs prints the proof under "equiv") -> R || B || C || challenge || randomness_response || value_response ||
+    commitment_response (src/proofs/commitment.rs:115-124), the 224-byte item of eg_commit_equiv_params_create."""
+    if ("proof" in obj) == ("equiv" in obj):
+        raise SerdeError('expected exactly one of the fields "proof" and "equiv"')
+    p = obj["proof"] if "proof" in obj else obj["equiv"]
+    return (_ct(obj["ciphertext"]) + b64url_decode(obj["commitment"]) + b64url_decode(p["challenge"]) +
+            b64url_decode(p["randomness_response"]) + b64url_decode(p["value_response"]) + b64url_decode(p["commitment_response"]))
+
+
 def pack_ballots(objs, packer=pack_encrypted_choice) -> bytes:
     """Concatenate many ballots; all must have the same packed size (same election parameters)."""
     parts = [packer(o) for o in objs]

@@ -121,8 +121,9 @@ typedef struct eg_qv_params eg_qv_params;         /* QuadraticVotingParams<Ristr
 
 /* ---- context ------------------------------------------------------------------------------------------------ */
 /* Version of this ABI: bumped whenever an exported function changes its prototype or meaning (6 = round 6: eg_msm_scratch_bytes_ctx,
- * d_ok mandatory in eg_points_prepare_device, the multi-GPU JSON entries).  A binding checks it once after loading the library. */
-#define EG_ABI_VERSION 6
+ * d_ok mandatory in eg_points_prepare_device, the multi-GPU JSON entries; 7 = round 7: EG_PROOF_COMMIT_EQUIV and the
+ * eg_commit_equiv_* entries).  A binding checks it once after loading the library. */
+#define EG_ABI_VERSION 7
 int eg_abi_version(void);
 int eg_init(int device, eg_ctx** out);   /* no reference analogue: the backend is a ZST */
 void eg_destroy(eg_ctx* ctx);
@@ -320,7 +321,7 @@ int eg_qv_tally_encode_multi(eg_qv_params* const* per_device, int n_dev, uint8_t
  *   with RangeDecomposition::optimal(upper_bound) (range.rs:148-153); eg_proof_item_size gives the stride.
  * status: EG_ST_OK, EG_ST_BAD_*, EG_ST_SUM_CHALLENGE (zero: ChallengeMismatch) or EG_ST_RANGE_CHALLENGE (bool/range). */
 typedef struct eg_proof_params eg_proof_params;
-enum { EG_PROOF_ZERO = 0, EG_PROOF_BOOL = 1, EG_PROOF_RANGE = 2, EG_PROOF_SHARE = 3, EG_PROOF_SUMSQ = 4 };
+enum { EG_PROOF_ZERO = 0, EG_PROOF_BOOL = 1, EG_PROOF_RANGE = 2, EG_PROOF_SHARE = 3, EG_PROOF_SUMSQ = 4, EG_PROOF_COMMIT_EQUIV = 5 };
 int eg_proof_params_create(eg_ctx*, const uint8_t pk[32], int kind, uint64_t upper_bound, eg_proof_params** out);
 /* PublicKeySet::verify_share (sharing/key_set.rs:209-228) for one participant: item = the ciphertext's
  * random element R(32) || decryption share dh(32) || challenge || response; status EG_ST_SUM_CHALLENGE on ChallengeMismatch.
@@ -333,6 +334,18 @@ int eg_share_params_create(eg_ctx*, const uint8_t shared_key[32], uint64_t share
  * EG_ST_BAD_* or EG_ST_QV_CREDIT_EQUIV_CHALLENGE (ChallengeMismatch).  A wrong number of responses (LenMismatch, mul.rs:197-202)
  * cannot be expressed in a packed item.  Verify with eg_verify_proof_batch. */
 int eg_sumsq_params_create(eg_ctx*, const uint8_t pk[32], int n_values, const char* label, size_t label_len, eg_proof_params** out);
+/* CommitmentEquivalenceProof::verify(ciphertext, receiver, commitment, commitment_blinding_base, transcript) (proofs/commitment.rs:186-238)
+ * with transcript = Transcript::new(label) (tests/snapshots.rs:163-177 uses b"test"): an ElGamal ciphertext (R, B) under `pk` and a
+ * Pedersen commitment C = [v]G + [r_c]H hide the same value.  item (224 B) = R || B (Ciphertext::to_bytes) || C || challenge ||
+ * randomness_response || value_response || commitment_response (struct order, commitment.rs:115-124); status EG_ST_OK, EG_ST_BAD_* with
+ * the item index 0..6, or EG_ST_SUM_CHALLENGE (ChallengeMismatch).  Verify with eg_verify_proof_batch.  A caller that goes on to use
+ * the transcript after the proof (examples/equivalence.rs hands it to Bulletproofs) is not served: every item starts a fresh transcript.
+ * blinding_base = H, the third fixed base of the params object, with comb tables of its own (0.8 GB, and the wide form with the other
+ * two).  It must decode and must NOT be the identity (EG_ERR_BAD_ARG): the reference accepts any element, but a commitment over the
+ * identity hides nothing, and an identity comb table is a case nothing in this library has ever built.  pk as for every params object
+ * (EG_ERR_BAD_PUBLIC_KEY); label up to 255 bytes. */
+int eg_commit_equiv_params_create(eg_ctx*, const uint8_t pk[32], const uint8_t blinding_base[32], const char* label, size_t label_len,
+                                  eg_proof_params** out);
 void eg_proof_params_destroy(eg_proof_params*);
 size_t eg_proof_item_size(const eg_proof_params*);
 int eg_verify_proof_batch(eg_proof_params*, size_t n, const uint8_t* items, uint32_t* status);
@@ -367,6 +380,18 @@ int eg_qv_encrypt_votes_batch(eg_qv_params*, uint64_t base_seed, size_t first, s
                               const uint32_t* votes /* n x n_options */, uint8_t* out);
 int eg_qv_encrypt_votes_batch_device(eg_qv_params*, uint64_t base_seed, size_t first, size_t n, uint64_t rng_skip,
                                      const void* d_votes, void* d_out, void* stream);
+
+/* CommitmentEquivalenceProof::new (proofs/commitment.rs:134-181) on a commitment-equivalence params object, VARIABLE TIME like the other
+ * generators (see TIMING): test and benchmark inputs only.  Item i encrypts values[i] and commits to it, drawing from
+ * ChaChaRng::seed_from_u64(base_seed + first + i) after rng_skip 64-byte draws, in the reference's order: r (CiphertextWithValue::new),
+ * r_c (SecretKey::generate), e_r, e_v, e_c.  (12345, rng_skip = 1), value 123, label "test" and the Bulletproofs blinding base
+ * reproduce the reference's `commitment-equiv-proof` snapshot byte for byte.  blindings (may be NULL): r_c of every item, 32 bytes
+ * each - what a caller needs to prove anything further about the commitment. */
+int eg_commit_equiv_prove_batch_device(eg_proof_params*, uint64_t base_seed, size_t first, size_t n, uint64_t rng_skip,
+                                       const void* d_values /* n x uint64 */, void* d_items /* n x 224 */,
+                                       void* d_blindings /* n x 32 or NULL */, void* stream);
+int eg_commit_equiv_prove_batch(eg_proof_params*, uint64_t base_seed, size_t first, size_t n, uint64_t rng_skip,
+                                const uint64_t* values, uint8_t* items, uint8_t* blindings /* or NULL */);
 
 /* ---- wire ingest (host only, no GPU needed) ------------------------------------------------------------
  * The reference's serde layout in human-readable formats (src/serde.rs:19-80,179-355: every scalar / element an unpadded base64url
@@ -475,7 +500,7 @@ int eg_verify_qv_json_begin_multi(eg_qv_params* const* per_device, int n_dev, in
  * RangeDecomposition::optimal(upper_bound).to_string() (range.rs:110-124,148-305): the string hashed into the transcript */
 int eg_range_decomposition(uint64_t upper_bound, char* buf, size_t cap);
 /* JSON summary of the verification plan: kind 0 single-choice, 1 multi-choice, 2 quadratic voting (credits), 3 verify_zero,
- * 4 verify_bool, 5 verify_range (upper bound), 6 sum-of-squares proof over n_options values */
+ * 4 verify_bool, 5 verify_range (upper bound), 6 sum-of-squares proof over n_options values, 7 commitment-equivalence proof */
 int eg_plan_describe(int kind, int n_options, uint64_t credits_or_bound, char* buf, size_t cap);
 
 /* ---- measurement hooks (bench.py) ------------------------------------------------------------------------------------------

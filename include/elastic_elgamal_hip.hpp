@@ -9,6 +9,7 @@
 //   QuadraticVotingBallot::verify (batched)   src/app/quadratic_voting.rs:291-329
 //   QuadraticVotingError                      src/app/quadratic_voting.rs:335-354
 //   VerificationError                         src/proofs/mod.rs:63-80
+//   CommitmentEquivalenceProof::verify / ::new (batched)   src/proofs/commitment.rs:186-238, 134-181
 //   Ristretto (Group backend, batched)        src/group/ristretto.rs:23-146
 #pragma once
 #include <array>
@@ -207,6 +208,53 @@ class QuadraticVotingParams {
   eg_qv_params* p_ = nullptr;
   size_t n_;
   uint64_t credits_ = 0;
+};
+
+// CommitmentEquivalenceProof::verify (batched; src/proofs/commitment.rs:186-238) with transcript = Transcript::new(label): the
+// ciphertext (R, B) for `receiver` and the Pedersen commitment C = [v]G + [r_c]H over `commitment_blinding_base` hide the same value.
+// Packed item (224 bytes): R || B || C || challenge || randomness_response || value_response || commitment_response.
+class CommitmentEquivalence {
+ public:
+  static constexpr size_t ITEM_SIZE = 224;
+  // an item the reference could not even deserialise: a non-canonical scalar or an invalid element at 32-byte item `item` of proof `index`
+  struct Malformed { size_t index; size_t item; bool scalar; };
+  // commitment_blinding_base must decode and must not be the identity (Error with EG_ERR_BAD_ARG; see eg_hip.h)
+  CommitmentEquivalence(const Context& ctx, const Element& receiver, const Element& commitment_blinding_base, const std::string& label) {
+    check(eg_commit_equiv_params_create(ctx.raw(), receiver.data(), commitment_blinding_base.data(), label.data(), label.size(), &p_));
+  }
+  ~CommitmentEquivalence() { eg_proof_params_destroy(p_); }
+  CommitmentEquivalence(const CommitmentEquivalence&) = delete;
+  CommitmentEquivalence& operator=(const CommitmentEquivalence&) = delete;
+  // per item: nullopt == Ok(()), else VerificationError::ChallengeMismatch.  Items that do not deserialise never reach verify() in the
+  // reference: they are listed in *malformed (and count as ChallengeMismatch in the result); without `malformed` they throw.
+  std::vector<std::optional<VerificationError>> verify(const Bytes& packed, std::vector<Malformed>* malformed = nullptr) const {
+    const size_t n = packed.size() / ITEM_SIZE;
+    if (n * ITEM_SIZE != packed.size()) throw Error(EG_ERR_BAD_ARG, "packed length is not a whole number of commitment-equivalence items");
+    std::vector<uint32_t> st(n);
+    check(eg_verify_proof_batch(p_, n, packed.data(), st.data()));
+    std::vector<std::optional<VerificationError>> out(n);
+    for (size_t i = 0; i < n; ++i) {
+      const uint32_t kind = EG_STATUS_KIND(st[i]);
+      if (kind == EG_ST_OK) continue;
+      out[i] = VerificationError::ChallengeMismatch;
+      if (kind != EG_ST_BAD_SCALAR && kind != EG_ST_BAD_POINT) continue;
+      if (!malformed) throw Error(EG_ERR_BAD_ARG, "item " + std::to_string(i) + " does not deserialise");
+      malformed->push_back({i, EG_STATUS_DETAIL(st[i]), kind == EG_ST_BAD_SCALAR});
+    }
+    return out;
+  }
+  // CommitmentEquivalenceProof::new for values[i] from ChaChaRng::seed_from_u64(base_seed + first + i) (commitment.rs:134-181); the
+  // blinding scalars r_c go to *blindings when given.  VARIABLE TIME (see eg_hip.h): test / synthetic data only.
+  Bytes prove_batch(uint64_t base_seed, size_t first, const std::vector<uint64_t>& values, std::vector<Scalar>* blindings = nullptr) const {
+    Bytes out(values.size() * ITEM_SIZE);
+    if (blindings) blindings->resize(values.size());
+    check(eg_commit_equiv_prove_batch(p_, base_seed, first, values.size(), 0, values.data(), out.data(),
+                                      blindings ? reinterpret_cast<uint8_t*>(blindings->data()) : nullptr));
+    return out;
+  }
+  eg_proof_params* raw() const { return p_; }
+ private:
+  eg_proof_params* p_ = nullptr;
 };
 
 // One batch over several GPUs of this process (eg_verify_*_batch_multi): per_device[d] = the election's params created on the context
