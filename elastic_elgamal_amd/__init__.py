@@ -188,6 +188,11 @@ def _load() -> C.CDLL:
         "eg_commit_equiv_params_create": (C.c_int, [vp, cp, cp, cp, sz, C.POINTER(vp)]),
         "eg_commit_equiv_prove_batch": (C.c_int, [vp, C.c_uint64, sz, sz, C.c_uint64, vp, vp, vp]),
         "eg_commit_equiv_prove_batch_device": (C.c_int, [vp, C.c_uint64, sz, sz, C.c_uint64, vp, vp, vp, vp]),
+        "eg_proof_prove_input_size": (sz, [vp]),
+        "eg_proof_prove_batch": (C.c_int, [vp, C.c_uint64, sz, sz, C.c_uint64, vp, vp]),
+        "eg_proof_prove_batch_device": (C.c_int, [vp, C.c_uint64, sz, sz, C.c_uint64, vp, vp, vp]),
+        "eg_share_prove_batch": (C.c_int, [vp, cp, C.c_uint64, sz, sz, C.c_uint64, vp, vp, vp]),
+        "eg_share_prove_batch_device": (C.c_int, [vp, cp, C.c_uint64, sz, sz, C.c_uint64, vp, vp, vp, vp]),
         "eg_merlin_challenge_batch": (C.c_int, [vp, sz, cp, sz, cp, sz, cp, sz, cp, sz, cp, sz]),
         "eg_choice_pack_json": (C.c_int, [C.c_int, C.c_int, cp, sz, C.c_int, sz, vp, vp, C.POINTER(sz)]),
         "eg_qv_pack_json": (C.c_int, [C.c_int, C.c_uint64, cp, sz, C.c_int, sz, vp, vp, C.POINTER(sz)]),
@@ -865,6 +870,7 @@ class PublicKeyVerifier:
     """Batched ``PublicKey::verify_zero / verify_bool / verify_range`` (src/keys/impls.rs:59-69,100-112,142-151)."""
 
     ZERO, BOOL, RANGE = 0, 1, 2
+    _value_rows = False      # prove() takes one value per item (a sum of squares: one row of values)
 
     def __init__(self, ctx: Context, public_key: bytes, kind: int, upper_bound: int = 0):
         self.ctx, self.kind = ctx, kind
@@ -885,6 +891,30 @@ class PublicKeyVerifier:
         """n items at device pointer d_items -> n status words (uint32) at d_status; asynchronous on `stream`."""
         _check(_load().eg_verify_proof_batch_device(self._h, n, d_items, d_status, stream))
 
+    def prove(self, base_seed: int, first: int, values_or_n, rng_skip: int = 0) -> bytes:
+        """``PublicKey::encrypt_zero / encrypt_bool / encrypt_range`` and ``SumOfSquaresProof::new`` on the GPU (test and benchmark
+        inputs: variable time); item i draws from ChaChaRng::seed_from_u64(base_seed + first + i) after `rng_skip` 64-byte draws.
+        `values_or_n`: the number of items for ZERO; one value per item for BOOL (0 / 1 / bool) and RANGE; one sequence of n_values
+        integers per item for a sum of squares.  Returns the packed items, as `verify_batch` takes them."""
+        per = _load().eg_proof_prove_input_size(self._h) // 8
+        if per == 0:
+            n, arr = int(values_or_n), None
+        else:
+            rows = list(values_or_n)
+            n = len(rows)
+            flat = [int(x) for row in rows for x in row] if self._value_rows else [int(v) for v in rows]
+            if len(flat) != n * per:
+                raise ValueError(f"every item needs {per} values")
+            arr = (C.c_uint64 * max(len(flat), 1))(*flat)
+        out = C.create_string_buffer(max(n * self.item_size, 1))
+        _check(_load().eg_proof_prove_batch(self._h, base_seed, first, n, rng_skip, arr, out))
+        return out.raw[: n * self.item_size]
+
+    def prove_device(self, base_seed: int, first: int, n: int, d_inputs: int, d_items: int, rng_skip: int = 0, stream: int = 0):
+        """The same on device buffers: the items' uint64 inputs at d_inputs (0 for ZERO) -> n items at d_items; asynchronous on
+        `stream`.  The inputs are trusted."""
+        _check(_load().eg_proof_prove_batch_device(self._h, base_seed, first, n, rng_skip, d_inputs or None, d_items, stream))
+
     def close(self):
         if getattr(self, "_h", None):
             _load().eg_proof_params_destroy(self._h)
@@ -900,6 +930,8 @@ class PublicKeyVerifier:
 class SumOfSquaresVerifier(PublicKeyVerifier):
     """Batched ``SumOfSquaresProof::verify`` (src/proofs/mul.rs:190-260) with ``Transcript::new(label)``.
     item = n value ciphertexts || sum-of-squares ciphertext || challenge || 2n ciphertext responses || sum response."""
+
+    _value_rows = True
 
     def __init__(self, ctx: Context, public_key: bytes, n_values: int, label: bytes):
         self.ctx, self.kind = ctx, 4
@@ -959,6 +991,26 @@ class DecryptionShareVerifier(PublicKeyVerifier):
         self._h = C.c_void_p()
         _check(_load().eg_share_params_create(ctx._h, shared_key, shares, threshold, index, participant_key, C.byref(self._h)))
         self.item_size = _load().eg_proof_item_size(self._h)
+
+    def prove(self, secret_share: bytes, base_seed: int, first: int, ct_randoms: bytes, rng_skip: int = 0):
+        """``ActiveParticipant::decrypt_share`` on the GPU for this participant (test and benchmark inputs: variable time in the secret
+        share): one item per 32-byte random element of `ct_randoms`, item i drawing from ChaChaRng::seed_from_u64(base_seed + first + i)
+        after `rng_skip` 64-byte draws.  Returns (packed items, ok bytes); an element that does not decode gets ok 0 and a zeroed item."""
+        if len(secret_share) != 32 or len(ct_randoms) % 32:
+            raise ValueError("secret_share and every random element are 32-byte encodings")
+        n = len(ct_randoms) // 32
+        out = C.create_string_buffer(max(n * self.item_size, 1))
+        ok = C.create_string_buffer(max(n, 1))
+        buf = (C.c_char * max(len(ct_randoms), 1)).from_buffer_copy(ct_randoms or b"\0")
+        _check(_load().eg_share_prove_batch(self._h, secret_share, base_seed, first, n, rng_skip, buf, out, ok))
+        return out.raw[: n * self.item_size], ok.raw[:n]
+
+    def prove_device(self, secret_share: bytes, base_seed: int, first: int, n: int, d_ct_randoms: int, d_items: int, d_ok: int,
+                     rng_skip: int = 0, stream: int = 0):
+        """The same on device buffers: n x 32 bytes at d_ct_randoms -> n items at d_items and n ok bytes at d_ok; asynchronous on
+        `stream`.  The secret share is trusted to be canonical."""
+        _check(_load().eg_share_prove_batch_device(self._h, secret_share, base_seed, first, n, rng_skip, d_ct_randoms, d_items, d_ok,
+                                                   stream))
 
 
 class QuadraticVotingParams(_BatchParams):

@@ -25,3 +25,27 @@ void eg_launch_commit_equiv_prove(int blocks, hipStream_t s, u64 seed0, size_t n
                                   const uint4* tabK, const uint4* tabH, const u32* prefixes, int pre, u32* out, u32* blindings) {
   hipLaunchKernelGGL(k_commit_equiv_prove, dim3(blocks), dim3(NT), 0, s, seed0, n, rng_skip, values, tabG, tabK, tabH, prefixes, pre, out, blindings);
 }
+
+// ---- provers of the single-item proofs (zero, bool / range, sum of squares, decryption share) ----
+void eg_launch_zero_prove(int blocks, hipStream_t s, u64 seed0, size_t n, u64 rng_skip, const uint4* tabG, const uint4* tabK,
+                          const u32* prefixes, int pre, u32* out) {
+  hipLaunchKernelGGL(k_zero_prove, dim3(blocks), dim3(NT), 0, s, seed0, n, rng_skip, tabG, tabK, prefixes, pre, out);
+}
+void eg_launch_range_prove(int blocks, hipStream_t s, u64 seed0, size_t n, u64 rng_skip, const u64* values, int n_rings, int pre_main,
+                           int pre_ring, const u32* d_desc, const uint4* tabG, const uint4* tabK, const u32* prefixes, u32* out,
+                           u32 stride_words, u32* gws) {
+  const GenRange r{n_rings, d_desc, pre_main, pre_ring};
+  hipLaunchKernelGGL(k_range_prove, dim3(blocks), dim3(NT), 0, s, seed0, n, rng_skip, values, r, tabG, tabK, prefixes, out, stride_words, gws);
+}
+void eg_launch_sumsq_prove(int blocks, hipStream_t s, u64 seed0, size_t n, u64 rng_skip, int n_values, const u64* values, int pre,
+                           const uint4* tabG, const uint4* tabK, const u32* prefixes, u32* out, u32 stride_words, u32* gws) {
+  hipLaunchKernelGGL(k_sumsq_prove, dim3(blocks), dim3(NT), 0, s, seed0, n, rng_skip, n_values, values, pre, tabG, tabK, prefixes, out,
+                     stride_words, gws);
+}
+void eg_launch_share_prove(int blocks, hipStream_t s, u64 seed0, size_t n, u64 rng_skip, const u32 secret[8], const u32 participant_key[8],
+                           const u32* ct_random, const uint4* tabG, const u32* prefixes, int pre, u32* out, unsigned char* ok, u32* gws) {
+  GenShareKey key;
+  for (int w = 0; w < 8; ++w) { key.secret[w] = secret[w]; key.participant_key[w] = participant_key[w]; }
+  hipLaunchKernelGGL(k_share_prove, dim3(blocks), dim3(NT), 0, s, seed0, n, rng_skip, key, ct_random, tabG, prefixes, pre, out, ok,
+                     reinterpret_cast<uint4*>(gws));
+}

@@ -41,6 +41,15 @@ void eg_launch_choice_encrypt(int blocks, hipStream_t s, u64 seed0, size_t n, in
                               int pre_logeq, u32* out, u32 stride_words, u32* gws);
 void eg_launch_commit_equiv_prove(int blocks, hipStream_t s, u64 seed0, size_t n, u64 rng_skip, const u64* values, const uint4* tabG,
                                   const uint4* tabK, const uint4* tabH, const u32* prefixes, int pre, u32* out, u32* blindings);
+void eg_launch_zero_prove(int blocks, hipStream_t s, u64 seed0, size_t n, u64 rng_skip, const uint4* tabG, const uint4* tabK,
+                          const u32* prefixes, int pre, u32* out);
+void eg_launch_range_prove(int blocks, hipStream_t s, u64 seed0, size_t n, u64 rng_skip, const u64* values, int n_rings, int pre_main,
+                           int pre_ring, const u32* d_desc, const uint4* tabG, const uint4* tabK, const u32* prefixes, u32* out,
+                           u32 stride_words, u32* gws);
+void eg_launch_sumsq_prove(int blocks, hipStream_t s, u64 seed0, size_t n, u64 rng_skip, int n_values, const u64* values, int pre,
+                           const uint4* tabG, const uint4* tabK, const u32* prefixes, u32* out, u32 stride_words, u32* gws);
+void eg_launch_share_prove(int blocks, hipStream_t s, u64 seed0, size_t n, u64 rng_skip, const u32 secret[8], const u32 participant_key[8],
+                           const u32* ct_random, const uint4* tabG, const u32* prefixes, int pre, u32* out, unsigned char* ok, u32* gws);
 unsigned eg_gen_choice_ws_words(int n_options);
 unsigned eg_gen_qv_ws_words(int n_options, unsigned max_rings, unsigned max_responses);
 
@@ -912,7 +921,11 @@ static int engine_verify_host(Engine* e, size_t n, const uint8_t* ballots, uint3
 // ---------------------------------------------------------------------------------------------------------------
 struct eg_choice_params { Engine* eng; int n_options; int single; };
 struct eg_qv_params { Engine* eng; int n_options; uint64_t credits; eghost::QvShape shape; };
-struct eg_proof_params { Engine* eng; int kind; size_t item_size; };
+struct eg_proof_params {
+  Engine* eng; int kind; size_t item_size;
+  // what the provers need beyond the plan: the decomposition of a range proof (bool: one ring over [O, G]) and the values of a sum of squares
+  uint64_t upper_bound = 0; eghost::RangeDecomposition range; int n_values = 0;
+};
 // between eg_verify_*_json_begin and eg_verify_json_end / _abort the params object belongs to the stream: its work sets, staging ring and
 // running tally are in use, so every other verify / tally call on it is refused
 static int refuse_if_streaming(const Engine* e) {
@@ -2000,6 +2013,8 @@ int eg_proof_params_create(eg_ctx* c, const uint8_t pk[32], int kind, uint64_t u
     TRY(engine_create(c, eghost::build_range_plan(upper_bound, &item), pk, 0, &e));
   } else return fail(EG_ERR_BAD_ARG, "unknown proof kind");
   *out = new eg_proof_params{e, kind, item};
+  if (kind == EG_PROOF_BOOL) (*out)->range.rings = {{2, 1}};
+  if (kind == EG_PROOF_RANGE) { (*out)->upper_bound = upper_bound; (*out)->range = eghost::optimal_range(upper_bound); }
   return EG_OK;
 }
 int eg_share_params_create(eg_ctx* c, const uint8_t shared_key[32], uint64_t shares, uint64_t threshold, uint64_t index,
@@ -2018,6 +2033,7 @@ int eg_sumsq_params_create(eg_ctx* c, const uint8_t pk[32], int n_values, const 
   size_t item = 0;
   TRY(engine_create(c, eghost::build_sumsq_plan(n_values, std::string(label ? label : "", label_len), &item), pk, 0, &e));
   *out = new eg_proof_params{e, EG_PROOF_SUMSQ, item};
+  (*out)->n_values = n_values;
   return EG_OK;
 }
 int eg_commit_equiv_params_create(eg_ctx* c, const uint8_t pk[32], const uint8_t blinding_base[32], const char* label, size_t label_len,
@@ -3070,6 +3086,113 @@ int eg_commit_equiv_prove_batch(eg_proof_params* p, uint64_t base_seed, size_t f
   TRY(commit_equiv_prove_device(p, base_seed, first, n, rng_skip, v.p, d.p, blindings ? b.p : nullptr, e->ctx->stream));
   TRY(d.get(items, n * eghost::COMMIT_EQUIV_ITEM, e->ctx->stream));
   if (blindings) TRY(b.get(blindings, n * 32, e->ctx->stream));
+  HIPCHK(hipStreamSynchronize(e->ctx->stream));
+  return EG_OK;
+}
+
+// ---- provers of the single-item proofs (prover_kernels.cuh: k_zero_prove, k_range_prove, k_sumsq_prove, k_share_prove) ----------------
+static_assert(EG_PROOF_ZERO == eghost::PROVE_ZERO && EG_PROOF_BOOL == eghost::PROVE_BOOL && EG_PROOF_RANGE == eghost::PROVE_RANGE &&
+              EG_PROOF_SHARE == eghost::PROVE_SHARE && EG_PROOF_SUMSQ == eghost::PROVE_SUMSQ, "host_plan.hpp names the kinds of eg_hip.h");
+size_t eg_proof_prove_input_size(const eg_proof_params* p) {
+  const int per = p ? eghost::prove_inputs_per_item(p->kind, p->n_values) : -1;
+  return per < 0 ? 0 : (size_t)per * 8;
+}
+static int proof_prove_device(eg_proof_params* p, uint64_t base_seed, size_t first, size_t n, uint64_t rng_skip, const void* d_inputs,
+                              void* d_items, hipStream_t s) {
+  Engine* e = p->eng;
+  HIPCHK(hipSetDevice(e->ctx->device));
+  if (n == 0) return EG_OK;
+  const u64* vals = reinterpret_cast<const u64*>(d_inputs);
+  u32* out = reinterpret_cast<u32*>(d_items);
+  int blocks = 0;
+  if (p->kind == EG_PROOF_ZERO) {
+    eg_launch_zero_prove(grid_for(n, e->ctx->cus * 4), s, base_seed + first, n, rng_skip, e->ctx->tabG, e->d_tabK, e->d_prefixes,
+                         e->plan.gen_pre_logeq, out);
+  } else if (p->kind == EG_PROOF_SUMSQ) {
+    TRY(gen_workspace(e, n, egplan::gen_sumsq_ws_words((u32)p->n_values), &blocks));
+    eg_launch_sumsq_prove(blocks, s, base_seed + first, n, rng_skip, p->n_values, vals, e->plan.gen_pre_sumsq, e->ctx->tabG, e->d_tabK,
+                          e->d_prefixes, out, (u32)(p->item_size / 4), e->gen_ws);
+  } else {     // bool and range: RangeProof::new over the object's decomposition
+    const auto& rings = p->range.rings;
+    if (!e->d_gen_desc) {
+      std::vector<u32> desc;
+      for (auto& r : rings) { desc.push_back((u32)r.size); desc.push_back((u32)r.step); }
+      HIPCHK(hipMalloc((void**)&e->d_gen_desc, desc.size() * sizeof(u32)));
+      HIPCHK(hipMemcpy(e->d_gen_desc, desc.data(), desc.size() * sizeof(u32), hipMemcpyHostToDevice));
+    }
+    TRY(gen_workspace(e, n, egplan::gen_range_ws_words((u32)rings.size(), (u32)p->range.rings_size()), &blocks));
+    eg_launch_range_prove(blocks, s, base_seed + first, n, rng_skip, vals, (int)rings.size(), e->plan.gen_pre_main, e->plan.gen_pre_ring,
+                          e->d_gen_desc, e->ctx->tabG, e->d_tabK, e->d_prefixes, out, (u32)(p->item_size / 4), e->gen_ws);
+  }
+  HIPCHK(hipGetLastError());
+  return EG_OK;
+}
+static int proof_prove_kind_ok(const eg_proof_params* p) {
+  if (eghost::prove_inputs_per_item(p->kind, p->n_values) < 0)
+    return fail(EG_ERR_BAD_ARG, p->kind == EG_PROOF_SHARE ? "a decryption share needs the secret share: eg_share_prove_batch"
+                                                          : "commitment-equivalence proofs have their own entry: eg_commit_equiv_prove_batch");
+  return EG_OK;
+}
+int eg_proof_prove_batch_device(eg_proof_params* p, uint64_t base_seed, size_t first, size_t n, uint64_t rng_skip, const void* d_inputs,
+                                void* d_items, void* stream) { EG_LOCK_P(p);
+  if (!p) return fail(EG_ERR_BAD_ARG, "bad argument");
+  TRY(proof_prove_kind_ok(p));
+  if (n && (!d_items || (!d_inputs && p->kind != EG_PROOF_ZERO))) return fail(EG_ERR_BAD_ARG, "bad argument");
+  return proof_prove_device(p, base_seed, first, n, rng_skip, d_inputs, d_items, (hipStream_t)stream);
+}
+int eg_proof_prove_batch(eg_proof_params* p, uint64_t base_seed, size_t first, size_t n, uint64_t rng_skip, const uint64_t* inputs,
+                         uint8_t* items) { EG_LOCK_P(p);
+  if (!p) return fail(EG_ERR_BAD_ARG, "bad argument");
+  TRY(proof_prove_kind_ok(p));
+  if (n && (!items || (!inputs && p->kind != EG_PROOF_ZERO))) return fail(EG_ERR_BAD_ARG, "bad argument");
+  if (const char* why = eghost::check_prove_inputs(p->kind, p->upper_bound, p->n_values, inputs, n)) return fail(EG_ERR_BAD_ARG, why);
+  Engine* e = p->eng;
+  HIPCHK(hipSetDevice(e->ctx->device));
+  const size_t in_bytes = n * eg_proof_prove_input_size(p);
+  DevBuf v, d;
+  TRY(v.alloc(in_bytes)); TRY(d.alloc(n * p->item_size));
+  TRY(v.put(inputs, in_bytes, e->ctx->stream));
+  TRY(proof_prove_device(p, base_seed, first, n, rng_skip, v.p, d.p, e->ctx->stream));
+  TRY(d.get(items, n * p->item_size, e->ctx->stream));
+  HIPCHK(hipStreamSynchronize(e->ctx->stream));
+  return EG_OK;
+}
+// ActiveParticipant::decrypt_share per item, with the radix-16 table of each R in the engine's generator workspace
+static int share_prove_device(eg_proof_params* p, const uint8_t secret_share[32], uint64_t base_seed, size_t first, size_t n,
+                              uint64_t rng_skip, const void* d_ct_random, void* d_items, void* d_ok, hipStream_t s) {
+  Engine* e = p->eng;
+  HIPCHK(hipSetDevice(e->ctx->device));
+  if (n == 0) return EG_OK;
+  u32 sk[8], key[8];
+  memcpy(sk, secret_share, 32);
+  memcpy(key, e->key_bytes, 32);
+  int blocks = 0;
+  TRY(gen_workspace(e, n, egplan::gen_share_ws_words(), &blocks));
+  eg_launch_share_prove(blocks, s, base_seed + first, n, rng_skip, sk, key, reinterpret_cast<const u32*>(d_ct_random), e->ctx->tabG,
+                        e->d_prefixes, e->plan.gen_pre_logeq, reinterpret_cast<u32*>(d_items), reinterpret_cast<unsigned char*>(d_ok),
+                        e->gen_ws);
+  HIPCHK(hipGetLastError());
+  return EG_OK;
+}
+int eg_share_prove_batch_device(eg_proof_params* p, const uint8_t secret_share[32], uint64_t base_seed, size_t first, size_t n,
+                                uint64_t rng_skip, const void* d_ct_random, void* d_items, void* d_ok, void* stream) { EG_LOCK_P(p);
+  if (!p || !secret_share || (n && (!d_ct_random || !d_items || !d_ok))) return fail(EG_ERR_BAD_ARG, "bad argument");
+  if (p->kind != EG_PROOF_SHARE) return fail(EG_ERR_BAD_ARG, "not a decryption-share params object");
+  return share_prove_device(p, secret_share, base_seed, first, n, rng_skip, d_ct_random, d_items, d_ok, (hipStream_t)stream);
+}
+int eg_share_prove_batch(eg_proof_params* p, const uint8_t secret_share[32], uint64_t base_seed, size_t first, size_t n, uint64_t rng_skip,
+                         const uint8_t* ct_random, uint8_t* items, uint8_t* ok) { EG_LOCK_P(p);
+  if (!p || !secret_share || (n && (!ct_random || !items || !ok))) return fail(EG_ERR_BAD_ARG, "bad argument");
+  if (p->kind != EG_PROOF_SHARE) return fail(EG_ERR_BAD_ARG, "not a decryption-share params object");
+  if (!eghost::scalar_bytes_canonical(secret_share)) return fail(EG_ERR_BAD_ARG, "the secret share is not a canonical scalar");
+  Engine* e = p->eng;
+  HIPCHK(hipSetDevice(e->ctx->device));
+  DevBuf r, d, o;
+  TRY(r.alloc(n * 32)); TRY(d.alloc(n * 128)); TRY(o.alloc(n));
+  TRY(r.put(ct_random, n * 32, e->ctx->stream));
+  TRY(share_prove_device(p, secret_share, base_seed, first, n, rng_skip, r.p, d.p, o.p, e->ctx->stream));
+  TRY(d.get(items, n * 128, e->ctx->stream));
+  TRY(o.get(ok, n, e->ctx->stream));
   HIPCHK(hipStreamSynchronize(e->ctx->stream));
   return EG_OK;
 }

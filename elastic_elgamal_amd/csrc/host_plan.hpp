@@ -186,7 +186,7 @@ struct Plan {
     return r;
   }
   int pk_off = -1;
-  int gen_pre_main = -1, gen_pre_ring = -1, gen_pre_logeq = -1;  // prefix indices used by the ballot generator
+  int gen_pre_main = -1, gen_pre_ring = -1, gen_pre_logeq = -1;  // prefix indices used by the ballot generator and the proof provers
   int gen_vote_main = -1, gen_vote_ring = -1, gen_credit_main = -1, gen_credit_ring = -1, gen_pre_sumsq = -1, gen_pre_cequiv = -1;
   uint32_t pk_ref() {  // 32 bytes of the election key; filled in when the params object is created
     if (pk_off < 0) { pk_off = (int)blob.size(); blob.insert(blob.end(), 32, 0); }
@@ -581,6 +581,7 @@ inline Plan build_zero_plan() {   // item = ct(64) || challenge || response
   const uint16_t R = P.wire_point(0), B = P.wire_point(1);
   P.wire_scalar(2); P.wire_scalar(3);
   const uint32_t pre = P.new_prefix();
+  P.gen_pre_logeq = (int)pre;
   P.prefix_programs.push_back({{OP_NEW, P.ref("zero_encryption"), 0, 0},
                                {OP_APPEND_BLOB, P.ref("dom-sep"), P.ref("log_eq"), 0},
                                {OP_APPEND_BLOB, P.ref("K"), P.pk_ref(), 0},
@@ -605,7 +606,7 @@ inline Plan build_bool_plan() {   // item = ct(64) || e0 || s0 || s1
   r.ptR = P.wire_point(0); r.ptB = P.wire_point(1);
   for (int i = 2; i < 5; ++i) P.wire_scalar((uint16_t)i);
   r.enc_from_wire = true; r.enc_item = 0; r.derive_level = 0; r.admissible = {0, 1}; r.resp_item = 3;
-  const uint16_t flag = add_ring_proof(P, {{OP_NEW, P.ref("bool_encryption"), 0, 0}}, {r}, 2);
+  const uint16_t flag = add_ring_proof(P, {{OP_NEW, P.ref("bool_encryption"), 0, 0}}, {r}, 2, 0, &P.gen_pre_main, &P.gen_pre_ring);
   P.rules.push_back({flag, 6});
   return P;
 }
@@ -613,6 +614,7 @@ inline Plan build_range_plan(uint64_t upper_bound, size_t* item_size) {   // ct 
   Plan P;
   const RangeDecomposition d = optimal_range(upper_bound);
   RangeOut r = add_range_proof(P, d, "ciphertext_range", 0);
+  P.gen_pre_main = r.pre_main; P.gen_pre_ring = r.pre_ring;
   P.stride = (size_t)r.n_items * 32;
   if (item_size) *item_size = P.stride;
   P.rules.push_back({r.flag, 6});
@@ -633,6 +635,7 @@ inline Plan build_sumsq_plan(int n, const std::string& label, size_t* item_size)
   for (int i = 0; i < 2 * n + 2; ++i) P.wire_scalar((uint16_t)(c_item + i));
   const uint16_t sz_item = (uint16_t)(c_item + 1 + 2 * n);
   const uint32_t pre = P.new_prefix();
+  P.gen_pre_sumsq = (int)pre;
   P.prefix_programs.push_back({{OP_NEW, P.ref(label), 0, 0},
                                {OP_APPEND_BLOB, P.ref("dom-sep"), P.ref("sum_of_squares"), 0},
                                {OP_APPEND_BLOB, P.ref("K"), P.pk_ref(), 0},
@@ -708,6 +711,7 @@ inline Plan build_share_plan(uint64_t shares, uint64_t threshold, const uint8_t 
   const uint16_t R = P.wire_point(0), dh = P.wire_point(1);
   P.wire_scalar(2); P.wire_scalar(3);
   const uint32_t pre = P.new_prefix();
+  P.gen_pre_logeq = (int)pre;
   const std::string shared(reinterpret_cast<const char*>(shared_key), 32);
   P.prefix_programs.push_back({{OP_NEW, P.ref("elgamal_decryption_share"), 0, 0},
                                {OP_APPEND_U64, P.ref("n"), (uint32_t)shares, 0},          // key_set.rs:167-171
@@ -729,6 +733,51 @@ inline Plan build_share_plan(uint64_t shares, uint64_t threshold, const uint8_t 
                               {OP_CHALLENGE_CHECK, P.ref("c"), 2, flag}});
   P.rules.push_back({flag, 4});
   return P;
+}
+
+// ---- inputs of the single-item provers (eg_proof_prove_batch, eg_share_prove_batch): what the reference asserts ---------------------
+// Kinds as EG_PROOF_* of eg_hip.h.  The host entries refuse what makes the reference panic; the device entries trust their caller.
+enum { PROVE_ZERO = 0, PROVE_BOOL = 1, PROVE_RANGE = 2, PROVE_SHARE = 3, PROVE_SUMSQ = 4 };
+// uint64 inputs per item: zero none, bool and range one value, sum of squares one per value; -1 for a kind this entry does not serve
+inline int prove_inputs_per_item(int kind, int n_values) {
+  switch (kind) {
+    case PROVE_ZERO: return 0;
+    case PROVE_BOOL: case PROVE_RANGE: return 1;
+    case PROVE_SUMSQ: return n_values;
+    default: return -1;
+  }
+}
+// null when every item's inputs are admissible, else what is wrong with the first one that is not: a bool above 1 (usize::from(bool)),
+// a range value at or above the upper bound (range.rs:478: assert!(value < range.upper_bound)), a sum of squares that does not fit the
+// u64 that CiphertextWithValue::new takes (summed in 128 bits: the reference's own `x * x` sum would overflow first)
+inline const char* check_prove_inputs(int kind, uint64_t upper_bound, int n_values, const uint64_t* inputs, size_t n) {
+  const int per = prove_inputs_per_item(kind, n_values);
+  if (per < 0) return "this proof kind has no value-driven prover";
+  if (per == 0 || n == 0) return nullptr;
+  if (!inputs) return "inputs missing";
+  for (size_t i = 0; i < n; ++i) {
+    const uint64_t* v = inputs + i * (size_t)per;
+    if (kind == PROVE_BOOL && v[0] > 1) return "a bool is 0 or 1";
+    if (kind == PROVE_RANGE && v[0] >= upper_bound) return "value out of range";
+    if (kind == PROVE_SUMSQ) {
+      unsigned __int128 sum = 0;
+      for (int k = 0; k < per; ++k) {
+        sum += (unsigned __int128)v[k] * v[k];
+        if (sum >> 64) return "the sum of squares does not fit 64 bits";
+      }
+    }
+  }
+  return nullptr;
+}
+// ScalarOps::deserialize_scalar (ristretto.rs:59-62): a little-endian 32-byte integer below the group order l
+inline bool scalar_bytes_canonical(const uint8_t s[32]) {
+  static const uint8_t L[32] = {0xed, 0xd3, 0xf5, 0x5c, 0x1a, 0x63, 0x12, 0x58, 0xd6, 0x9c, 0xf7, 0xa2, 0xde, 0xf9, 0xde, 0x14,
+                                0,    0,    0,    0,    0,    0,    0,    0,    0,    0,    0,    0,    0,    0,    0,    0x10};
+  for (int i = 31; i >= 0; --i) {
+    if (s[i] < L[i]) return true;
+    if (s[i] > L[i]) return false;
+  }
+  return false;
 }
 
 // ---- flattening of a plan into the arrays the kernels index (pure host logic, sanitizer-tested in tests/hostcheck) ------------

@@ -89,4 +89,12 @@ struct WireItem {
 
 inline uint32_t blob_ref(uint32_t off, uint32_t len) { return (off << 12) | len; }
 
+// ---- per-lane workspace of the prover kernels (prover_kernels.cuh), in 32-bit words: sized on the host, indexed on the device ----
+// one range proof: per ring 33 words (value index +0, r +1, x +9, terminal R_G +17, R_K +25), then 8 words per response in ring order
+constexpr uint32_t gen_range_ws_words(uint32_t n_rings, uint32_t total_responses) { return 33u * n_rings + 8u * total_responses; }
+// one sum-of-squares proof: the values [0, n), then 24 words per value (ciphertext randomness +0, e_r +8, e_x +16)
+constexpr uint32_t gen_sumsq_ws_words(uint32_t n_values) { return 25u * n_values; }
+// one decryption share: the radix-16 table {1..8}R of the ciphertext's random element, 8 entries of 36 words
+constexpr uint32_t gen_share_ws_words() { return 8u * 36u; }
+
 }  // namespace egplan

@@ -303,8 +303,10 @@ __device__ __noinline__ void gen_sim_commitments(u32 cg[8], u32 ck[8], const Fix
 }
 
 // workspace of one range proof at word offset rb: per ring 33 words (value index +0, r +1, x +9, terminal R_G +17, R_K +25),
-// then 8 words per response in ring order
-__host__ __device__ inline u32 gen_range_ws_words(u32 n_rings, u32 total_responses) { return 33u * n_rings + 8u * total_responses; }
+// then 8 words per response in ring order (plan.h, where the host code and its CPU tests see the same count)
+using egplan::gen_range_ws_words;
+using egplan::gen_sumsq_ws_words;
+using egplan::gen_share_ws_words;
 
 // RangeProof::new for `value` with randomness drawn from rng; writes ct || partials || e0 || responses at `ob`
 // (words) and returns the ciphertext randomness in r_out.
@@ -460,9 +462,75 @@ __device__ __noinline__ void gen_range_proof(Transcript<LdsState>& t, ChaChaRng&
   (void)total;
 }
 
+// SumOfSquaresProof::new (mul.rs:107-181) over ciphertexts the lane has just made: value k's ciphertext at ob + k * ct_stride (words),
+// the sum-of-squares ciphertext at zb with randomness sum_r; workspace as gen_sumsq_ws_words: value k at word k, its ciphertext
+// randomness at n + 24 k (e_r and e_x are parked at +8 and +16).  Draws e_z, then e_r, e_x per value.  Writes c || (s_r, s_x) per value
+// || s_z at sp.  Shared by k_qv_encrypt (votes and credit) and k_sumsq_prove (the stand-alone proof).
+__device__ __noinline__ void gen_sumsq_proof(Transcript<LdsState>& t, ChaChaRng& rng, u32 NO, const u32* ob, u32 ct_stride, const u32* zb,
+                                             u32* sp, const u32 sum_r[8], const FixedTable& tg, const FixedTable& tk, const u32* prefix,
+                                             const LaneWs& ws) {
+  const u32 per = NO;
+  gen_import(t, prefix);
+  u32 e_z[8], sum_rand[8];
+  rng_scalar(rng, e_z);
+#pragma unroll
+  for (int w = 0; w < 8; ++w) sum_rand[w] = sum_r[w];
+  u32 acc_g[8] = {0, 0, 0, 0, 0, 0, 0, 0}, acc_k[8];   // sum e_x v  and  sum e_x r + e_z
+#pragma unroll
+  for (int w = 0; w < 8; ++w) acc_k[w] = e_z[w];
+#pragma unroll 1
+  for (u32 k = 0; k < NO; ++k) {
+    const u32* vct = ob + (size_t)k * ct_stride;
+    gen_append32(t, "R_x", 3, vct);
+    gen_append32(t, "X", 1, vct + 8);
+    u32 c0[8], c1[8], xs[8], nx[8], er[8], ex[8], vr[8];
+    ws.ld8(vr, per + 24u * k);
+    rng_scalar(rng, er);
+    fixed2_encode(c0, tg, er, tk, nullptr);
+    gen_append32(t, "[e_r]G", 6, c0);
+    rng_scalar(rng, ex);
+    fixed2_encode(c1, tg, ex, tk, er);
+    gen_append32(t, "[e_x]G + [e_r]K", 15, c1);
+    ws.st8(per + 24u * k + 8, er);
+    ws.st8(per + 24u * k + 16, ex);
+    sc_from_u64(xs, (u64)ws.ld(k));
+    sc_neg(nx, xs);
+    gen_muladd(sum_rand, vr, nx, sum_rand);      // sum_random_scalar += r_x * (-x)
+    gen_muladd(acc_g, ex, xs, acc_g);
+    gen_muladd(acc_k, ex, vr, acc_k);
+  }
+  u32 rsum[8], vsum[8];
+  fixed2_encode(rsum, tg, acc_k, tk, nullptr);        // sum e_x R_x + e_z G
+  fixed2_encode(vsum, tg, acc_g, tk, acc_k);          // sum e_x X + e_z K
+  gen_append32(t, "R_z", 3, zb);
+  gen_append32(t, "Z", 1, zb + 8);
+  gen_append32(t, "[e_x]R_x + [e_z]G", 17, rsum);
+  gen_append32(t, "[e_x]X + [e_z]K", 15, vsum);
+  u32 c[8];
+  gen_challenge(t, c);
+#pragma unroll
+  for (int w = 0; w < 8; ++w) sp[w] = c[w];
+#pragma unroll 1
+  for (u32 k = 0; k < NO; ++k) {
+    u32 s_r[8], s_x[8], xs[8], er[8], ex[8], vr[8];
+    ws.ld8(vr, per + 24u * k);
+    ws.ld8(er, per + 24u * k + 8);
+    ws.ld8(ex, per + 24u * k + 16);
+    sc_from_u64(xs, (u64)ws.ld(k));
+    gen_muladd(s_r, c, vr, er);
+    gen_muladd(s_x, c, xs, ex);
+#pragma unroll
+    for (int w = 0; w < 8; ++w) { sp[(size_t)(1 + 2 * k) * 8 + w] = s_r[w]; sp[(size_t)(2 + 2 * k) * 8 + w] = s_x[w]; }
+  }
+  u32 s_z[8];
+  gen_muladd(s_z, c, sum_rand, e_z);
+#pragma unroll
+  for (int w = 0; w < 8; ++w) sp[(size_t)(1 + 2 * NO) * 8 + w] = s_z[w];
+}
+
 // quadratic voting: votes [0, n), then 24 words per option (ciphertext randomness +0, e_r +8, e_x +16), then one range-proof area
 __host__ __device__ inline u32 gen_qv_ws_words(int n_options, u32 max_rings, u32 max_responses) {
-  return (u32)n_options * 25u + gen_range_ws_words(max_rings, max_responses);
+  return gen_sumsq_ws_words((u32)n_options) + gen_range_ws_words(max_rings, max_responses);
 }
 
 // votes_in: null = votes drawn from the second stream; else n_options words per voter (QuadraticVotingBallot::new(params, votes,
@@ -521,64 +589,7 @@ __global__ void __launch_bounds__(NT) k_qv_encrypt(u64 seed0, size_t n, int n_op
     }
     u32* cb = ob + (size_t)n_options * vote_words;
     gen_range_proof(t, rng, credit_range, credit, tg, tk, prefixes, cb, credit_r, ws, rb);
-    // SumOfSquaresProof::new (mul.rs:107-181)
-    u32* sp = cb + credit_words;
-    gen_import(t, prefixes + (size_t)pre_sumsq * 52);
-    u32 e_z[8], sum_rand[8];
-    rng_scalar(rng, e_z);
-#pragma unroll
-    for (int w = 0; w < 8; ++w) sum_rand[w] = credit_r[w];
-    u32 acc_g[8] = {0, 0, 0, 0, 0, 0, 0, 0}, acc_k[8];   // sum e_x v  and  sum e_x r + e_z
-#pragma unroll
-    for (int w = 0; w < 8; ++w) acc_k[w] = e_z[w];
-#pragma unroll 1
-    for (u32 k = 0; k < NO; ++k) {
-      const u32* vct = ob + (size_t)k * vote_words;
-      gen_append32(t, "R_x", 3, vct);
-      gen_append32(t, "X", 1, vct + 8);
-      u32 c0[8], c1[8], xs[8], nx[8], er[8], ex[8], vr[8];
-      ws.ld8(vr, per + 24u * k);
-      rng_scalar(rng, er);
-      fixed2_encode(c0, tg, er, tk, nullptr);
-      gen_append32(t, "[e_r]G", 6, c0);
-      rng_scalar(rng, ex);
-      fixed2_encode(c1, tg, ex, tk, er);
-      gen_append32(t, "[e_x]G + [e_r]K", 15, c1);
-      ws.st8(per + 24u * k + 8, er);
-      ws.st8(per + 24u * k + 16, ex);
-      sc_from_u64(xs, (u64)ws.ld(k));
-      sc_neg(nx, xs);
-      gen_muladd(sum_rand, vr, nx, sum_rand);      // sum_random_scalar += r_x * (-x)
-      gen_muladd(acc_g, ex, xs, acc_g);
-      gen_muladd(acc_k, ex, vr, acc_k);
-    }
-    u32 rsum[8], vsum[8];
-    fixed2_encode(rsum, tg, acc_k, tk, nullptr);        // sum e_x R_x + e_z G
-    fixed2_encode(vsum, tg, acc_g, tk, acc_k);          // sum e_x X + e_z K
-    gen_append32(t, "R_z", 3, cb);
-    gen_append32(t, "Z", 1, cb + 8);
-    gen_append32(t, "[e_x]R_x + [e_z]G", 17, rsum);
-    gen_append32(t, "[e_x]X + [e_z]K", 15, vsum);
-    u32 c[8];
-    gen_challenge(t, c);
-#pragma unroll
-    for (int w = 0; w < 8; ++w) sp[w] = c[w];
-#pragma unroll 1
-    for (u32 k = 0; k < NO; ++k) {
-      u32 s_r[8], s_x[8], xs[8], er[8], ex[8], vr[8];
-      ws.ld8(vr, per + 24u * k);
-      ws.ld8(er, per + 24u * k + 8);
-      ws.ld8(ex, per + 24u * k + 16);
-      sc_from_u64(xs, (u64)ws.ld(k));
-      gen_muladd(s_r, c, vr, er);
-      gen_muladd(s_x, c, xs, ex);
-#pragma unroll
-      for (int w = 0; w < 8; ++w) { sp[(size_t)(1 + 2 * k) * 8 + w] = s_r[w]; sp[(size_t)(2 + 2 * k) * 8 + w] = s_x[w]; }
-    }
-    u32 s_z[8];
-    gen_muladd(s_z, c, sum_rand, e_z);
-#pragma unroll
-    for (int w = 0; w < 8; ++w) sp[(size_t)(1 + 2 * n_options) * 8 + w] = s_z[w];
+    gen_sumsq_proof(t, rng, NO, ob, vote_words, cb, cb + credit_words, credit_r, tg, tk, prefixes + (size_t)pre_sumsq * 52, ws);
   }
 }
 
@@ -636,6 +647,174 @@ __global__ void __launch_bounds__(NT) k_commit_equiv_prove(u64 seed0, size_t n, 
 #pragma unroll
       for (int w = 0; w < 8; ++w) blindings[i * 8 + w] = rc[w];
     }
+  }
+}
+
+// =====================================================================================================================
+// The provers of the single-item proofs that eg_verify_proof_batch checks (eg_hip.h, "batch tier: single-ciphertext proofs"): one item
+// per lane, item i from ChaChaRng::seed_from_u64(seed0 + i) after rng_skip draws, packed as the verifier reads them.
+// =====================================================================================================================
+
+// PublicKey::encrypt_zero (keys/impls.rs:31-52) + LogEqualityProof::new (log_equality.rs:114-139).  Draws r, then x.
+// out: 128-byte items ([r]G || [r]K || c || s).  `pre` = the zero plan's prefix (label, dom-sep, K).
+__global__ void __launch_bounds__(NT) k_zero_prove(u64 seed0, size_t n, u64 rng_skip, const uint4* tabG, const uint4* tabK,
+                                                   const u32* prefixes, int pre, u32* out) {
+  __shared__ u32 lds[50 * NT];
+  const FixedTable tg(tabG), tk(tabK);
+  for (size_t i = (size_t)blockIdx.x * NT + threadIdx.x; i < n; i += (size_t)gridDim.x * NT) {
+    ChaChaRng rng;
+    chacha_seed_from_u64(rng, seed0 + i);
+    rng.counter = rng_skip;
+    u32 r[8], x[8], enc[8], c[8], s[8];
+    u32* ob = out + i * 32;
+    Transcript<LdsState> t;
+    t.st.base = lds + threadIdx.x;
+    gen_import(t, prefixes + (size_t)pre * 52);
+    rng_scalar(rng, r);
+    fixed2_encode(enc, tg, r, tk, nullptr);
+    gen_append32(t, "[r]G", 4, enc);
+#pragma unroll
+    for (int w = 0; w < 8; ++w) ob[w] = enc[w];
+    fixed2_encode(enc, tg, nullptr, tk, r);
+    gen_append32(t, "[r]K", 4, enc);
+#pragma unroll
+    for (int w = 0; w < 8; ++w) ob[8 + w] = enc[w];
+    rng_scalar(rng, x);
+    fixed2_encode(enc, tg, x, tk, nullptr);
+    gen_append32(t, "[x]G", 4, enc);
+    fixed2_encode(enc, tg, nullptr, tk, x);
+    gen_append32(t, "[x]K", 4, enc);
+    gen_challenge(t, c);
+    gen_muladd(s, c, r, x);
+#pragma unroll
+    for (int w = 0; w < 8; ++w) { ob[16 + w] = c[w]; ob[24 + w] = s[w]; }
+  }
+}
+
+// PublicKey::encrypt_range (keys/impls.rs:124-133) = RangeProof::new under the range plan's prefixes, and PublicKey::encrypt_bool
+// (:77-89): RingProofBuilder with ONE ring over [O, G] - gen_range_proof with the description (size 2, step 1) and the bool plan's
+// prefixes, which carry no range header.  values: one u64 per item.  Workspace: gen_range_ws_words of the decomposition.
+__global__ void __launch_bounds__(NT) k_range_prove(u64 seed0, size_t n, u64 rng_skip, const u64* values, GenRange range,
+                                                    const uint4* tabG, const uint4* tabK, const u32* prefixes, u32* out, u32 stride_words,
+                                                    u32* gws) {
+  __shared__ u32 lds[50 * NT];
+  const FixedTable tg(tabG), tk(tabK);
+  const LaneWs ws{gws + ((size_t)blockIdx.x * NT + threadIdx.x), (size_t)gridDim.x * NT};
+  for (size_t i = (size_t)blockIdx.x * NT + threadIdx.x; i < n; i += (size_t)gridDim.x * NT) {
+    ChaChaRng rng;
+    chacha_seed_from_u64(rng, seed0 + i);
+    rng.counter = rng_skip;
+    Transcript<LdsState> t;
+    t.st.base = lds + threadIdx.x;
+    u32 r[8];
+    gen_range_proof(t, rng, range, values[i], tg, tk, prefixes, out + i * stride_words, r, ws, 0);
+  }
+}
+
+// SumOfSquaresProof::new on fresh ciphertexts, in the order of tests/snapshots.rs:128-150: the ciphertext of sum(v^2) is drawn FIRST
+// (r_z), then one r per value, then the proof's draws (gen_sumsq_proof).  values: n_values u64 per item, sum of squares below 2^64 (so
+// every value fits 32 bits).  out: value ciphertexts || sum ciphertext || c || responses || s_z - the sum ciphertext is STORED after the
+// values.  Workspace: gen_sumsq_ws_words(n_values).
+__global__ void __launch_bounds__(NT) k_sumsq_prove(u64 seed0, size_t n, u64 rng_skip, int n_values, const u64* values, int pre,
+                                                    const uint4* tabG, const uint4* tabK, const u32* prefixes, u32* out, u32 stride_words,
+                                                    u32* gws) {
+  __shared__ u32 lds[50 * NT];
+  const FixedTable tg(tabG), tk(tabK);
+  const LaneWs ws{gws + ((size_t)blockIdx.x * NT + threadIdx.x), (size_t)gridDim.x * NT};
+  const u32 NV = (u32)n_values;
+  for (size_t i = (size_t)blockIdx.x * NT + threadIdx.x; i < n; i += (size_t)gridDim.x * NT) {
+    ChaChaRng rng;
+    chacha_seed_from_u64(rng, seed0 + i);
+    rng.counter = rng_skip;
+    u32* ob = out + i * stride_words;
+    u32* zb = ob + (size_t)NV * 16;
+    u64 sum = 0;
+    for (u32 k = 0; k < NV; ++k) {
+      const u64 v = values[i * (size_t)NV + k];
+      ws.st(k, (u32)v);
+      sum += v * v;
+    }
+    u32 rz[8], vsc[8], enc[8];
+    rng_scalar(rng, rz);
+    sc_from_u64(vsc, sum);
+    fixed2_encode(enc, tg, rz, tk, nullptr);
+#pragma unroll
+    for (int w = 0; w < 8; ++w) zb[w] = enc[w];
+    fixed2_encode(enc, tg, vsc, tk, rz);
+#pragma unroll
+    for (int w = 0; w < 8; ++w) zb[8 + w] = enc[w];
+#pragma unroll 1
+    for (u32 k = 0; k < NV; ++k) {
+      u32 r[8];
+      rng_scalar(rng, r);
+      sc_from_u64(vsc, (u64)ws.ld(k));
+      fixed2_encode(enc, tg, r, tk, nullptr);
+#pragma unroll
+      for (int w = 0; w < 8; ++w) ob[k * 16 + w] = enc[w];
+      fixed2_encode(enc, tg, vsc, tk, r);
+#pragma unroll
+      for (int w = 0; w < 8; ++w) ob[k * 16 + 8 + w] = enc[w];
+      ws.st8(NV + 24u * k, r);
+    }
+    Transcript<LdsState> t;
+    t.st.base = lds + threadIdx.x;
+    gen_sumsq_proof(t, rng, NV, ob, 16, zb, zb + 16, rz, tg, tk, prefixes + (size_t)pre * 52, ws);
+  }
+}
+
+// ActiveParticipant::decrypt_share (sharing/participant.rs:163-186): dh = [sk]R and a LogEqualityProof whose second base is the
+// ciphertext's random element R - a per-item base that is multiplied twice ([sk]R, [x]R), so it gets the radix-16 table {1..8}R of the
+// direct equation kernels (ge_var_table_build / ge_var_mul, 1152 bytes per lane in `tables`) and no comb table.
+// Draws x only.  `pre` = the share plan's prefix (label, key-set commitment, "i", dom-sep); the participant key bytes are hashed as given.
+// out: 128-byte items (R || dh || c || s); an R that does not decode gets a zeroed item and ok[i] = 0.
+struct GenShareKey { u32 secret[8], participant_key[8]; };
+__device__ __noinline__ void gen_var_mul_encode(u32 out[8], WsTable& tab, const u32 k[8]) {
+  u32 dg[8];
+  sc_recode_radix16(dg, k);
+  ge acc;
+  ge_var_mul(acc, tab, dg);
+  ristretto_encode(out, acc);
+}
+__global__ void __launch_bounds__(NT) k_share_prove(u64 seed0, size_t n, u64 rng_skip, GenShareKey key, const u32* ct_random,
+                                                    const uint4* tabG, const u32* prefixes, int pre, u32* out, unsigned char* ok,
+                                                    uint4* tables) {
+  __shared__ u32 lds[50 * NT];
+  const FixedTable tg(tabG);
+  WsTable tab;
+  tab.init(tables);
+  for (size_t i = (size_t)blockIdx.x * NT + threadIdx.x; i < n; i += (size_t)gridDim.x * NT) {
+    u32 rw[8];
+#pragma unroll
+    for (int w = 0; w < 8; ++w) rw[w] = ct_random[i * 8 + w];
+    u32* ob = out + i * 32;
+    ge R;
+    if (!ristretto_decode(R, rw)) {
+      for (int w = 0; w < 32; ++w) ob[w] = 0u;
+      ok[i] = 0;
+      continue;
+    }
+    ChaChaRng rng;
+    chacha_seed_from_u64(rng, seed0 + i);
+    rng.counter = rng_skip;
+    u32 x[8], dh[8], enc[8], c[8], s[8];
+    ge_var_table_build(tab, R);
+    gen_var_mul_encode(dh, tab, key.secret);
+    Transcript<LdsState> t;
+    t.st.base = lds + threadIdx.x;
+    gen_import(t, prefixes + (size_t)pre * 52);
+    gen_append32(t, "K", 1, rw);
+    gen_append32(t, "[r]G", 4, key.participant_key);
+    gen_append32(t, "[r]K", 4, dh);
+    rng_scalar(rng, x);
+    fixed2_encode(enc, tg, x, tg, nullptr);
+    gen_append32(t, "[x]G", 4, enc);
+    gen_var_mul_encode(enc, tab, x);
+    gen_append32(t, "[x]K", 4, enc);
+    gen_challenge(t, c);
+    gen_muladd(s, c, key.secret, x);
+#pragma unroll
+    for (int w = 0; w < 8; ++w) { ob[w] = rw[w]; ob[8 + w] = dh[w]; ob[16 + w] = c[w]; ob[24 + w] = s[w]; }
+    ok[i] = 1;
   }
 }
 

@@ -351,9 +351,11 @@ size_t eg_proof_item_size(const eg_proof_params*);
 int eg_verify_proof_batch(eg_proof_params*, size_t n, const uint8_t* items, uint32_t* status);
 int eg_verify_proof_batch_device(eg_proof_params*, size_t n, const void* d_items, void* d_status, void* stream);
 
-/* ---- synthetic ballots on the GPU (EncryptedChoice::new / QuadraticVotingBallot::new) ---------
- * VARIABLE TIME in the choices / votes and in the RNG-drawn secrets (see TIMING at the top): these entry points make test and benchmark
- * inputs; they are not a voting client.
+/* ---- synthetic ballots and proofs on the GPU (EncryptedChoice::new / QuadraticVotingBallot::new, and the provers
+ * of every proof kind that eg_verify_proof_batch checks) ---------
+ * VARIABLE TIME in the choices / votes / values and in every RNG-drawn secret, and for the decryption-share prover in the SECRET SHARE
+ * itself (a radix-16 ladder indexed by its digits; see TIMING at the top): these entry points make test and benchmark inputs; they are
+ * not a voting client and not a tallier.
  * Ballot i of the call is produced from ChaChaRng::seed_from_u64(base_seed + first + i) with the reference's
  * RNG draw order (choice.rs:313-349, ring.rs:54-194, log_equality.rs:114-139, range.rs:462-534, mul.rs:107-181);
  * the voter's selection comes from a second stream seeded with the complemented seed.  n_selected is only
@@ -392,6 +394,35 @@ int eg_commit_equiv_prove_batch_device(eg_proof_params*, uint64_t base_seed, siz
                                        void* d_blindings /* n x 32 or NULL */, void* stream);
 int eg_commit_equiv_prove_batch(eg_proof_params*, uint64_t base_seed, size_t first, size_t n, uint64_t rng_skip,
                                 const uint64_t* values, uint8_t* items, uint8_t* blindings /* or NULL */);
+
+/* The provers of the other single-item proofs, on the params objects that verify them (eg_proof_params_create, eg_sumsq_params_create):
+ *   EG_PROOF_ZERO   PublicKey::encrypt_zero (keys/impls.rs:31-52): no input; draws r, x.
+ *   EG_PROOF_BOOL   PublicKey::encrypt_bool (:77-89): one uint64 per item, 0 or 1.
+ *   EG_PROOF_RANGE  PublicKey::encrypt_range (:124-133) with RangeDecomposition::optimal(upper_bound): one uint64 per item, < upper_bound.
+ *   EG_PROOF_SUMSQ  SumOfSquaresProof::new (mul.rs:107-181) on fresh ciphertexts, as tests/snapshots.rs:128-150 makes them: n_values
+ *                   uint64 per item; the ciphertext of sum(v^2) is drawn FIRST, then one per value, then the proof's own draws.
+ * Item i draws from ChaChaRng::seed_from_u64(base_seed + first + i) after rng_skip 64-byte draws, in the reference's order, and is
+ * written in the layout eg_verify_proof_batch reads (eg_proof_item_size).  (12345, rng_skip = 1) reproduces the reference's
+ * `zero-encryption`, `bool-encryption` (true), `range-encryption` (bound 100, value 42) and `sum-sq-proof` ([1, 3, 3, 7, 5], label
+ * "test") snapshots byte for byte.  eg_proof_prove_input_size = bytes of input per item (0, 8, 8, 8 n_values; d_inputs / inputs may be
+ * NULL for EG_PROOF_ZERO only).  EG_ERR_BAD_ARG for EG_PROOF_SHARE (needs the secret: below) and EG_PROOF_COMMIT_EQUIV (its own entry
+ * above also returns the blindings).  The host form refuses, with EG_ERR_BAD_ARG, what makes the reference panic or overflow: a bool
+ * above 1, a value >= upper_bound, a sum of squares >= 2^64; the device form trusts its inputs. */
+size_t eg_proof_prove_input_size(const eg_proof_params*);
+int eg_proof_prove_batch_device(eg_proof_params*, uint64_t base_seed, size_t first, size_t n, uint64_t rng_skip,
+                                const void* d_inputs /* uint64 values; NULL for zero */, void* d_items, void* stream);
+int eg_proof_prove_batch(eg_proof_params*, uint64_t base_seed, size_t first, size_t n, uint64_t rng_skip,
+                         const uint64_t* inputs, uint8_t* items);
+/* ActiveParticipant::decrypt_share (sharing/participant.rs:163-186) on a params object of eg_share_params_create, for the participant
+ * whose key it holds: item i = R_i || dh = [secret_share]R_i || challenge || response (128 B, what eg_verify_proof_batch reads) for the
+ * ciphertext random element R_i = ct_random + 32 i; draws x only.  ok[i] = 0 and a zeroed item where R_i does not decode; the other
+ * items are unaffected.  It is NOT checked that [secret_share]G is the participant key: a wrong share gives items that do not verify,
+ * as in the reference (log_equality.rs:111-113).  The host form refuses a non-canonical secret_share (EG_ERR_BAD_ARG). */
+int eg_share_prove_batch_device(eg_proof_params*, const uint8_t secret_share[32], uint64_t base_seed, size_t first, size_t n,
+                                uint64_t rng_skip, const void* d_ct_random /* n x 32 */, void* d_items /* n x 128 */,
+                                void* d_ok /* n bytes */, void* stream);
+int eg_share_prove_batch(eg_proof_params*, const uint8_t secret_share[32], uint64_t base_seed, size_t first, size_t n,
+                         uint64_t rng_skip, const uint8_t* ct_random, uint8_t* items, uint8_t* ok);
 
 /* ---- wire ingest (host only, no GPU needed) ------------------------------------------------------------
  * The reference's serde layout in human-readable formats (src/serde.rs:19-80,179-355: every scalar / element an unpadded base64url

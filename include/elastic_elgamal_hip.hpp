@@ -257,6 +257,94 @@ class CommitmentEquivalence {
   eg_proof_params* p_ = nullptr;
 };
 
+// The other single-item proofs (eg_hip.h, "batch tier: single-ciphertext proofs"): one params object per proof kind, verified with
+// eg_verify_proof_batch and PRODUCED on the GPU by the provers below.  Every prover is VARIABLE TIME (see eg_hip.h): test / synthetic
+// data only.  Item i draws from ChaChaRng::seed_from_u64(base_seed + first + i) after rng_skip 64-byte draws.
+class ProofParams {
+ public:
+  ~ProofParams() { eg_proof_params_destroy(p_); }
+  ProofParams(const ProofParams&) = delete;
+  ProofParams& operator=(const ProofParams&) = delete;
+  size_t item_size() const { return eg_proof_item_size(p_); }
+  std::vector<uint32_t> verify_batch(const Bytes& packed) const {       // status words of eg_hip.h, one per item
+    const size_t n = packed.size() / item_size();
+    if (n * item_size() != packed.size()) throw Error(EG_ERR_BAD_ARG, "packed length is not a whole number of items");
+    std::vector<uint32_t> st(n);
+    check(eg_verify_proof_batch(p_, n, packed.data(), st.data()));
+    return st;
+  }
+  eg_proof_params* raw() const { return p_; }
+ protected:
+  ProofParams() = default;
+  // n items from the flat uint64 inputs (eg_proof_prove_input_size / 8 per item; none for the zero proof)
+  Bytes prove_values(uint64_t base_seed, size_t first, size_t n, const std::vector<uint64_t>& inputs, uint64_t rng_skip) const {
+    if (inputs.size() * 8 != n * eg_proof_prove_input_size(p_)) throw Error(EG_ERR_BAD_ARG, "wrong number of input values");
+    Bytes out(n * item_size());
+    check(eg_proof_prove_batch(p_, base_seed, first, n, rng_skip, inputs.data(), out.data()));
+    return out;
+  }
+  eg_proof_params* p_ = nullptr;
+};
+// PublicKey::encrypt_zero / verify_zero (src/keys/impls.rs:31-69): item = ciphertext || challenge || response
+class ZeroEncryption : public ProofParams {
+ public:
+  ZeroEncryption(const Context& ctx, const Element& receiver) { check(eg_proof_params_create(ctx.raw(), receiver.data(), EG_PROOF_ZERO, 0, &p_)); }
+  Bytes encrypt_zero(uint64_t base_seed, size_t first, size_t n, uint64_t rng_skip = 0) const { return prove_values(base_seed, first, n, {}, rng_skip); }
+};
+// PublicKey::encrypt_bool / verify_bool (:77-112): item = ciphertext || e0 || s0 || s1
+class BoolEncryption : public ProofParams {
+ public:
+  BoolEncryption(const Context& ctx, const Element& receiver) { check(eg_proof_params_create(ctx.raw(), receiver.data(), EG_PROOF_BOOL, 0, &p_)); }
+  Bytes encrypt_bool(uint64_t base_seed, size_t first, const std::vector<bool>& values, uint64_t rng_skip = 0) const {
+    return prove_values(base_seed, first, values.size(), std::vector<uint64_t>(values.begin(), values.end()), rng_skip);
+  }
+};
+// PublicKey::encrypt_range / verify_range (:124-151) with RangeDecomposition::optimal(upper_bound); values below upper_bound
+class RangeEncryption : public ProofParams {
+ public:
+  RangeEncryption(const Context& ctx, const Element& receiver, uint64_t upper_bound) {
+    check(eg_proof_params_create(ctx.raw(), receiver.data(), EG_PROOF_RANGE, upper_bound, &p_));
+  }
+  Bytes encrypt_range(uint64_t base_seed, size_t first, const std::vector<uint64_t>& values, uint64_t rng_skip = 0) const {
+    return prove_values(base_seed, first, values.size(), values, rng_skip);
+  }
+};
+// SumOfSquaresProof::new / verify (src/proofs/mul.rs:107-260) with Transcript::new(label) over n_values fresh ciphertexts per item:
+// item = value ciphertexts || sum-of-squares ciphertext || challenge || ciphertext responses || sum response
+class SumOfSquares : public ProofParams {
+ public:
+  SumOfSquares(const Context& ctx, const Element& receiver, size_t n_values, const std::string& label) : n_values_(n_values) {
+    check(eg_sumsq_params_create(ctx.raw(), receiver.data(), (int)n_values, label.data(), label.size(), &p_));
+  }
+  // values: n_values per item, back to back; the sum of an item's squares must fit 64 bits
+  Bytes prove(uint64_t base_seed, size_t first, const std::vector<uint64_t>& values, uint64_t rng_skip = 0) const {
+    return prove_values(base_seed, first, values.size() / n_values_, values, rng_skip);
+  }
+ private:
+  size_t n_values_;
+};
+// PublicKeySet::verify_share / ActiveParticipant::decrypt_share (src/sharing/key_set.rs:209-228, participant.rs:163-186) for ONE
+// participant of a key set: item = ciphertext.random_element || dh_element || challenge || response
+class DecryptionShares : public ProofParams {
+ public:
+  DecryptionShares(const Context& ctx, const Element& shared_key, uint64_t shares, uint64_t threshold, uint64_t index, const Element& participant_key) {
+    check(eg_share_params_create(ctx.raw(), shared_key.data(), shares, threshold, index, participant_key.data(), &p_));
+  }
+  // one item per random element; (*ok)[i] = 0 and a zeroed item where it does not decode (without `ok` that throws).  Variable time in
+  // the secret share.
+  Bytes decrypt_share(const Scalar& secret_share, uint64_t base_seed, size_t first, const std::vector<Element>& random_elements,
+                      std::vector<uint8_t>* ok = nullptr, uint64_t rng_skip = 0) const {
+    const size_t n = random_elements.size();
+    Bytes out(n * 128);
+    std::vector<uint8_t> good(n);
+    check(eg_share_prove_batch(p_, secret_share.data(), base_seed, first, n, rng_skip, reinterpret_cast<const uint8_t*>(random_elements.data()),
+                               out.data(), good.data()));
+    if (ok) *ok = good;
+    else for (uint8_t g : good) if (!g) throw Error(EG_ERR_BAD_ARG, "a ciphertext's random element is not a valid ristretto255 encoding");
+    return out;
+  }
+};
+
 // One batch over several GPUs of this process (eg_verify_*_batch_multi): per_device[d] = the election's params created on the context
 // of GPU d; contiguous slabs, one host thread per GPU inside the library, the slabs' tallies merged in the library.  What a
 // single-process host like examples/voting.rs:179-213 calls when the node has more than one GPU.
