@@ -158,6 +158,10 @@ def _load() -> C.CDLL:
         "eg_qv_ballot_size": (sz, [vp]),
         "eg_verify_qv_batch": (C.c_int, [vp, sz, vp, vp, vp]),
         "eg_verify_qv_batch_device": (C.c_int, [vp, sz, vp, vp, vp]),
+        "eg_verify_choice_small": (C.c_int, [vp, sz, vp, vp, vp]),
+        "eg_verify_choice_small_device": (C.c_int, [vp, sz, vp, vp, vp]),
+        "eg_verify_qv_small": (C.c_int, [vp, sz, vp, vp, vp]),
+        "eg_verify_qv_small_device": (C.c_int, [vp, sz, vp, vp, vp]),
         "eg_qv_tally_reset": (C.c_int, [vp]),
         "eg_qv_tally_encode": (C.c_int, [vp, cp]),
         "eg_verify_choice_batch_multi": (C.c_int, [C.POINTER(vp), C.c_int, sz, vp, vp, vp]),
@@ -233,6 +237,7 @@ def _load() -> C.CDLL:
 
 PACK_RESHAPE = 0xFFFFFFFE
 ABI_VERSION = 7          # include/eg_hip.h: EG_ABI_VERSION
+SMALL_BATCH_MAX = 4096   # include/eg_hip.h: EG_SMALL_BATCH_MAX, the most ballots one verify_small call takes
 
 
 def pack_json(text, n_options: int, single: bool | None = None, credits: int | None = None, threads: int = 0, max_objects: int = 0):
@@ -778,6 +783,24 @@ class _BatchParams:
     def verify_batch_device(self, n: int, d_ballots: int, d_status: int, stream: int = 0):
         """Asynchronous device-pointer variant (torch tensors' data_ptr()); tally accumulates on the device."""
         fn = getattr(_load(), f"eg_verify_{self._prefix}_batch_device")
+        _check(fn(self._h, n, d_ballots, d_status, stream))
+
+    def verify_small(self, ballots: bytes, with_tally: bool = True):
+        """verify_batch for a handful of ballots (at most SMALL_BATCH_MAX) with low latency: one workgroup per ballot in one launch
+        (eg_verify_*_small).  Same results, same running tally; returns (status words, tally of this call or None)."""
+        n = len(ballots) // self.ballot_size
+        if n * self.ballot_size != len(ballots):
+            raise ValueError("ballots is not a whole number of packed ballots")
+        st = (C.c_uint32 * max(n, 1))()
+        tally = C.create_string_buffer(64 * self.n_options) if with_tally else None
+        buf = (C.c_char * max(len(ballots), 1)).from_buffer_copy(ballots or b"\0")
+        fn = getattr(_load(), f"eg_verify_{self._prefix}_small")
+        _check(fn(self._h, n, buf, st, tally))
+        return list(st[:n]), (tally.raw if with_tally else None)
+
+    def verify_small_device(self, n: int, d_ballots: int, d_status: int, stream: int = 0):
+        """Asynchronous device-pointer variant of verify_small; the tally accumulates on the device."""
+        fn = getattr(_load(), f"eg_verify_{self._prefix}_small_device")
         _check(fn(self._h, n, d_ballots, d_status, stream))
 
     def prepare_wide_tables(self):

@@ -27,6 +27,7 @@
 #include "host_plan.hpp"
 #include "wire_json.hpp"
 #include "kernels.cuh"
+#include "latency_kernels.cuh"
 #include "pippenger.cuh"
 
 using namespace eg;
@@ -327,6 +328,14 @@ struct Engine {
   u32* gen_ws = nullptr;
   size_t gen_ws_bytes = 0;
   u32* d_gen_desc = nullptr;
+  // small-batch path (k_ballot_small): the stage and level tables on the device, the block size the plan asks for, and the workspace of
+  // the equations without a comb table (grown on demand; null for plans that have none)
+  StageDev* d_small_stages = nullptr;
+  LevelDev* d_small_levels = nullptr;
+  int small_threads = 0;
+  bool small_needs_ws = false;
+  uint4* small_ws = nullptr;
+  size_t small_ws_ballots = 0;
 };
 
 static int grid_for(size_t lanes, int cap_blocks);
@@ -352,7 +361,8 @@ static void engine_free(Engine* e) {
   if (!e) return;
   void* ptrs[] = {e->d_pt_items, e->d_sc_items, e->d_dclasses, e->d_dterms, e->d_jobs, e->d_vterms, e->d_insts, e->d_ops,
                   e->d_rules, e->d_tally_slots, e->d_base_slots, e->d_sum_bases, e->d_sum_members, e->d_acc_sums, e->d_acc_members, e->d_defer_slots, e->d_blob, e->d_cpts, e->d_prefixes, e->d_key_words,
-                  e->tally_saved, e->tally_saved2, e->tally_saved3, e->d_tally_enc, e->d_wire, e->d_status, e->gen_ws, e->d_gen_desc, e->d_h_srcs, e->d_h_words};
+                  e->tally_saved, e->tally_saved2, e->tally_saved3, e->d_tally_enc, e->d_wire, e->d_status, e->gen_ws, e->d_gen_desc, e->d_h_srcs, e->d_h_words,
+                  e->d_small_stages, e->d_small_levels, e->small_ws};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   for (auto& w : e->set) {
     void* sp[] = {w.pts, w.cmp, w.chal, w.states, w.flags, w.bad_item, w.btab, w.dpt, w.sacc, w.encw, w.partial, w.tally};
@@ -801,6 +811,77 @@ static int engine_verify_device(Engine* e, size_t n, const void* d_ballots, void
   return EG_OK;
 }
 
+// ---- the small-batch path: one launch of k_ballot_small (one workgroup per ballot, latency_kernels.cuh), then the batch path's tally ----
+// Same contract as engine_verify_device for n <= EG_SMALL_BATCH_MAX: verdicts in d_status, accepted ballots added to the running tally.
+// It works in work set 0 like a one-set batch call, so it takes both halves of the context's workspace protocol: calls of either
+// kind on one params object are then ordered on the GPU whatever streams they use.  The narrow comb tables are read always (a
+// handful of ballots does not pay for the wide ones), and every comb table of a ballot is resident whatever ring-group walk the
+// plan was built with - the walk's table slots are re-used stage by stage exactly as the batch path re-uses them.
+static int engine_small_prepare(Engine* e, size_t n, hipStream_t s) {
+  if (!e->small_threads) {
+    // k_ballot_small has no counterpart of k_eq_direct_h: an equation with a term over the third fixed base H would come out without it
+    if (e->plan.has_h()) return fail(EG_ERR_BAD_ARG, "internal: the small-batch path does not evaluate terms over a third fixed base");
+    int quads = 1;
+    bool needs_ws = false;
+    for (auto& st : e->stages) {
+      quads = std::max(quads, std::max(st.build_count, st.fam_count[FAM_TABLE1]));
+      if (st.fam_count[FAM_DIRECT1] || st.fam_count[FAM_GENERIC]) needs_ws = true;
+    }
+    int rc;
+    if ((rc = upload(&e->d_small_stages, e->stages, s))) return rc;
+    if ((rc = upload(&e->d_small_levels, e->levels, s))) return rc;
+    e->small_needs_ws = needs_ws;
+    e->small_threads = std::min(SM_MAX_THREADS, std::max(64, (quads * 4 + 63) / 64 * 64));
+  }
+  if (e->small_needs_ws && n > e->small_ws_ballots) {
+    HIPCHK(hipDeviceSynchronize());     // an earlier small call may still use the old slice
+    if (e->small_ws) (void)hipFree(e->small_ws);
+    e->small_ws = nullptr; e->small_ws_ballots = 0;
+    size_t cap = 64;
+    while (cap < n) cap *= 2;
+    HIPCHK(hipMalloc((void**)&e->small_ws, cap * SM_LANES * WS_QUADS * sizeof(uint4)));
+    e->small_ws_ballots = cap;
+  }
+  return EG_OK;
+}
+static int engine_verify_small_device(Engine* e, size_t n, const void* d_ballots, void* d_status, hipStream_t s) {
+  eg_ctx* ctx = e->ctx;
+  const eghost::Plan& P = e->plan;
+  if (!n) return EG_OK;
+  int rc;
+  if ((rc = engine_small_prepare(e, n, s))) return rc;
+  if ((rc = engine_reserve(e, (u32)((n + NT - 1) / NT * NT)))) return rc;
+  size_t all_idx = 0;
+  if ((rc = prof_begin(ctx, s, PROF_CALL, &all_idx))) return rc;
+  TRY_(ws_acquire(ctx, 3u, s));
+  ScopeExit release_ws{[&]() { (void)ws_release(ctx, 3u, s); }};
+  const Engine::WorkSet& w = e->set[0];
+  EngineBufs B = make_bufs(e, 0, d_ballots, (u32)n, d_status);
+  B.tabG = ctx->tabG; B.tabK = e->d_tabK; B.tabH = e->d_tabH;
+  SmallPlanDev D;
+  D.pt_items = e->d_pt_items; D.sc_items = e->d_sc_items; D.n_pt = (int)P.pt_items.size(); D.n_sc = (int)P.sc_items.size();
+  D.dclasses = e->d_dclasses; D.dterms = e->d_dterms;
+  D.levels = e->d_small_levels; D.n_levels = (int)e->levels.size();
+  D.stages = e->d_small_stages; D.n_stages = (int)e->stages.size();
+  D.jobs = e->d_jobs; D.vterms = e->d_vterms; D.insts = e->d_insts; D.ops = e->d_ops;
+  D.rules = e->d_rules; D.n_rules = (int)P.rules.size();
+  D.base_slots = e->d_base_slots;
+  D.sums = e->d_sum_bases; D.sum_members = e->d_sum_members; D.n_sums = e->n_sums;
+  D.acc_sums = e->d_acc_sums; D.acc_members = e->d_acc_members;
+  D.defer_slots = e->d_defer_slots;
+  D.ws = e->small_ws;
+  EG_WITH_TEETH(e->teeth, hipLaunchKernelGGL(k_ballot_small<T>, dim3((unsigned)n), dim3(e->small_threads), 0, s, B, D));
+  if (!P.tally_slots.empty()) {
+    const int G = std::min<int>(e->tally_blocks, (int)((n + NT - 1) / NT));
+    hipLaunchKernelGGL(k_tally_partial, dim3(G, (unsigned)P.tally_slots.size()), dim3(NT), 0, s, B, e->d_tally_slots, w.partial);
+    hipLaunchKernelGGL(k_tally_final, dim3((unsigned)P.tally_slots.size()), dim3(NT), 0, s, w.partial, G, w.tally);
+  }
+  if ((rc = prof_end(ctx, s, all_idx))) return rc;
+  if ((rc = engine_touch(e, s))) return rc;
+  HIPCHK(hipGetLastError());
+  return EG_OK;
+}
+
 // encodes a tally held in device memory (the running tally, or a snapshot of it) into host bytes
 static int engine_tally_encode_from(Engine* e, const u32* d_tally, uint8_t* out, bool drain_device = true) {
   hipStream_t s = e->ctx->stream;
@@ -845,7 +926,7 @@ static int engine_stage_reserve(Engine* e, size_t n) {
   return EG_OK;
 }
 
-static int engine_verify_host(Engine* e, size_t n, const uint8_t* ballots, uint32_t* status, uint8_t* tally_out) {
+static int engine_verify_host(Engine* e, size_t n, const uint8_t* ballots, uint32_t* status, uint8_t* tally_out, bool small = false) {
   hipStream_t s = e->ctx->stream;
   HIPCHK(hipSetDevice(e->ctx->device));
   // The host form runs on the context's own stream but shares the engine's workspaces and running tally with whatever
@@ -869,7 +950,7 @@ static int engine_verify_host(Engine* e, size_t n, const uint8_t* ballots, uint3
     hipLaunchKernelGGL(k_tally_init, dim3(blocks_of((size_t)ns)), dim3(NT), 0, s, e->tally, ns);
     set_aside = true;
   }
-  if (n && e->items_seen + n >= e->ctx->big_min) {     // the whole batch counts: its first piece already reads the wide comb tables
+  if (n && !small && e->items_seen + n >= e->ctx->big_min) {     // the whole batch counts: its first piece already reads the wide comb tables
     const int rc = ensure_big_tables(e, s);
     if (rc) return rc;
   }
@@ -903,7 +984,8 @@ static int engine_verify_host(Engine* e, size_t n, const uint8_t* ballots, uint3
       if (he == hipSuccess) he = hipEventRecord(uploaded[k], e->copy_stream);
       if (he == hipSuccess) he = hipStreamWaitEvent(s, uploaded[k], 0);
       if (he != hipSuccess) { rc = fail(EG_ERR_HIP, std::string("host upload: ") + hipGetErrorString(he)); break; }
-      rc = engine_verify_device(e, m, e->d_wire + off * e->plan.stride, e->d_status + off, s);
+      rc = small ? engine_verify_small_device(e, m, e->d_wire + off * e->plan.stride, e->d_status + off, s)
+                 : engine_verify_device(e, m, e->d_wire + off * e->plan.stride, e->d_status + off, s);
     }
     // one download at the end: a device-to-pageable copy would stall the host (and the next upload) behind chunk k
     if (rc == EG_OK && hipMemcpyAsync(status, e->d_status, n * sizeof(u32), hipMemcpyDeviceToHost, s) != hipSuccess)
@@ -1720,6 +1802,37 @@ int eg_qv_tally_encode(eg_qv_params* p, uint8_t* out) { EG_LOCK_P(p);
   return engine_tally_encode(p->eng, out);
 }
 
+// ---- small-batch tier: the same arguments and meaning as the batch entries, for at most EG_SMALL_BATCH_MAX ballots per call ----------
+extern "C++" {
+template <class Params>
+static int verify_small_host(std::unique_lock<std::recursive_mutex>& lk_, Params* p, size_t n, const uint8_t* ballots, uint32_t* status, uint8_t* tally_out) {
+  if (n > EG_SMALL_BATCH_MAX) return fail(EG_ERR_BAD_ARG, "more than EG_SMALL_BATCH_MAX ballots: use the batch entry");
+  if (!p || (n && (!ballots || !status))) return fail(EG_ERR_BAD_ARG, "bad argument");
+  EG_WAIT_JSON(p->eng);
+  return engine_verify_host(p->eng, n, ballots, status, tally_out, true);
+}
+template <class Params>
+static int verify_small_dev(std::unique_lock<std::recursive_mutex>& lk_, Params* p, size_t n, const void* d_ballots, void* d_status, void* stream) {
+  if (n > EG_SMALL_BATCH_MAX) return fail(EG_ERR_BAD_ARG, "more than EG_SMALL_BATCH_MAX ballots: use the batch entry");
+  if (!p || (n && (!d_ballots || !d_status))) return fail(EG_ERR_BAD_ARG, "bad argument");
+  EG_WAIT_JSON(p->eng);
+  HIPCHK(hipSetDevice(p->eng->ctx->device));
+  return engine_verify_small_device(p->eng, n, d_ballots, d_status, (hipStream_t)stream);
+}
+}  // extern "C++"
+int eg_verify_choice_small(eg_choice_params* p, size_t n, const uint8_t* ballots, uint32_t* status, uint8_t* tally_out) { EG_LOCK_P(p);
+  return verify_small_host(lk_, p, n, ballots, status, tally_out);
+}
+int eg_verify_choice_small_device(eg_choice_params* p, size_t n, const void* d_ballots, void* d_status, void* stream) { EG_LOCK_P(p);
+  return verify_small_dev(lk_, p, n, d_ballots, d_status, stream);
+}
+int eg_verify_qv_small(eg_qv_params* p, size_t n, const uint8_t* ballots, uint32_t* status, uint8_t* tally_out) { EG_LOCK_P(p);
+  return verify_small_host(lk_, p, n, ballots, status, tally_out);
+}
+int eg_verify_qv_small_device(eg_qv_params* p, size_t n, const void* d_ballots, void* d_status, void* stream) { EG_LOCK_P(p);
+  return verify_small_dev(lk_, p, n, d_ballots, d_status, stream);
+}
+
 // ---- batch tier, several GPUs in ONE process (the `device_mask` of the batch entry; examples/voting.rs:179-213 is one
 // single-threaded host process) ------------------------------------------------------------------------------------------------
 // per_device[d] is a params object of the same election created on its own context (normally one context per GPU).  The batch is
@@ -2190,7 +2303,7 @@ static egwire::CheckItemsFn make_check_items(eg_ctx* c) {
     return true;
   };
 }
-static int engine_verify_host(Engine* e, size_t n, const uint8_t* ballots, uint32_t* status, uint8_t* tally_out);
+static int engine_verify_host(Engine* e, size_t n, const uint8_t* ballots, uint32_t* status, uint8_t* tally_out, bool small);
 static egwire::VerifyPackedFn make_verify_packed(Engine* e) {
   return [e](size_t n, const egwire::Bytes& packed, std::vector<uint32_t>& status) {
     status.assign(n, 0);

@@ -271,6 +271,24 @@ int eg_qv_tally_add(eg_qv_params*, const uint8_t* in);
 int eg_qv_tally_reset_async(eg_qv_params*, void* stream);
 int eg_qv_tally_encode_device(eg_qv_params*, void* d_out, void* stream);
 
+/* ---- small-batch tier: a handful of ballots with low latency ---------------------------------------------------------------
+ * The batch entries chain about twenty kernels with one lane per group equation: whatever the batch, a call takes the ~2 ms of one
+ * lane's dependent chain.  The _small entries verify each ballot in ONE workgroup of ONE launch, with four lanes per point
+ * operation.  Arguments, status words, error precedence, the running tally, tally_out, locking and the refusal while a JSON stream is
+ * open are those of eg_verify_*_batch[_device]; n == 0 is EG_OK, n > EG_SMALL_BATCH_MAX is EG_ERR_BAD_ARG.  They work for every election
+ * shape the batch entries accept.  Measured crossover (profiles/r09_small_batch.txt, device-resident ballots, call + synchronize,
+ * small entry against batch entry): choice ballots - up to 1 024 ballots per call use the _small entry, above it the batch entry
+ * (5 options, single choice: 1.09 against 2.13 ms for one ballot, 1.21 against 2.03 for 256, 1.30 against 2.07 for 1 024, 4.44 against
+ * 2.11 for 4 096; 3-of-16 multi-choice 1.05 against 2.53 for one, 2.24 against 2.41 for 1 024, 8.28 against 3.23 for 4 096);
+ * quadratic-voting ballots - up to 256 per call use the _small entry (3.58 against 6.09 ms for one, 3.94 against 5.76 for 256, 8.27
+ * against 5.86 for 1 024).  One workgroup per ballot is sized for latency, not for throughput.  One ballot is faster through the
+ * _small entry than on one CPU core of the same host (1.09 against 1.25 ms, the reference-equivalent CPU verifier). */
+#define EG_SMALL_BATCH_MAX 4096   /* the flat part of the batch path's latency curve, DESIGN.md section 6 */
+int eg_verify_choice_small(eg_choice_params*, size_t n, const uint8_t* ballots, uint32_t* status, uint8_t* tally_out);
+int eg_verify_choice_small_device(eg_choice_params*, size_t n, const void* d_ballots, void* d_status, void* stream);
+int eg_verify_qv_small(eg_qv_params*, size_t n, const uint8_t* ballots, uint32_t* status, uint8_t* tally_out);
+int eg_verify_qv_small_device(eg_qv_params*, size_t n, const void* d_ballots, void* d_status, void* stream);
+
 /* ---- batch tier on several GPUs of ONE process (SURVEY.md 8b `device_mask`; the reference's host is one single-threaded process,
  * examples/voting.rs:179-213) -----------------------------------------------------------------------------------------------------
  * per_device[d], d < n_dev: params objects of the SAME election (same key, options, kind), each created on its own context

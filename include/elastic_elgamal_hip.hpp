@@ -141,6 +141,23 @@ class ChoiceParams {
     v.totals = unpack_totals(tally);
     return v;
   }
+  // the same for a handful of ballots (at most EG_SMALL_BATCH_MAX) with low latency: one workgroup per ballot in one launch
+  BatchVerdict<ChoiceVerificationError> verify_small(const Bytes& packed) const {
+    const size_t n = packed.size() / ballot_size();
+    if (n * ballot_size() != packed.size())
+      throw Error(EG_ERR_BAD_ARG, "packed length is not a whole number of ballots for these parameters");
+    std::vector<uint32_t> st(n);
+    Bytes tally(64 * n_);
+    check(eg_verify_choice_small(p_, n, packed.data(), st.data(), tally.data()));
+    BatchVerdict<ChoiceVerificationError> v;
+    for (uint32_t s : st) v.results.push_back(choice_error_from_status(s));
+    v.totals = unpack_totals(tally);
+    return v;
+  }
+  // asynchronous device-pointer form of verify_small: verdicts into d_status, accepted ballots into the running tally
+  void verify_small_device(size_t n, const void* d_ballots, void* d_status, void* stream = nullptr) const {
+    check(eg_verify_choice_small_device(p_, n, d_ballots, d_status, stream));
+  }
   // EncryptedChoice::new for synthetic voters base_seed + first + i (choice.rs:313-349), packed
   Bytes encrypt_batch(uint64_t base_seed, size_t first, size_t n, int n_selected = 0) const {
     Bytes out(n * ballot_size());
@@ -193,6 +210,21 @@ class QuadraticVotingParams {
     for (uint32_t s : st) v.results.push_back(qv_error_from_status(s));
     v.totals = unpack_totals(tally);
     return v;
+  }
+  // the same for a handful of ballots (at most EG_SMALL_BATCH_MAX) with low latency: one workgroup per ballot in one launch
+  BatchVerdict<QuadraticVotingError> verify_small(const Bytes& packed) const {
+    const size_t n = packed.size() / ballot_size();
+    if (n * ballot_size() != packed.size()) throw Error(EG_ERR_BAD_ARG, "packed length is not a whole number of ballots");
+    std::vector<uint32_t> st(n);
+    Bytes tally(64 * n_);
+    check(eg_verify_qv_small(p_, n, packed.data(), st.data(), tally.data()));
+    BatchVerdict<QuadraticVotingError> v;
+    for (uint32_t s : st) v.results.push_back(qv_error_from_status(s));
+    v.totals = unpack_totals(tally);
+    return v;
+  }
+  void verify_small_device(size_t n, const void* d_ballots, void* d_status, void* stream = nullptr) const {
+    check(eg_verify_qv_small_device(p_, n, d_ballots, d_status, stream));
   }
   // QuadraticVotingBallot::new(&params, votes, rng) for voters base_seed + first + i (quadratic_voting.rs:234-284); votes:
   // options_count() numbers per voter with sum(v^2) <= credits.  VARIABLE TIME in the votes (see eg_hip.h): test / synthetic data only.

@@ -1,6 +1,7 @@
 #!/bin/bash
 # Developer helper: build an alternate libeg_hip.so with extra -D flags for A/B runs (EG_LIB=build_variants/libeg_NAME.so).
 # usage: tools/build_variant.sh NAME [-DFLAG ...]
+# e.g.   tools/build_variant.sh ab1 -DEG_SMALL_AB=1     (after git apply tools/variants/small_batch_ab.patch; tools/variants/README.md)
 set -e
 cd "$(dirname "$0")/.."
 name=$1; shift

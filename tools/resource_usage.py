@@ -23,6 +23,17 @@ seen, out = set(), []
 out.append(f"# hipcc --offload-arch=gfx950 -O3 -std=c++17 -Rpass-analysis=kernel-resource-usage -c eg_hip.hip eg_gen.hip   (tools/resource_usage.py {tag})")
 out.append("# VGPR/AGPR per lane, scratch bytes per lane, waves per SIMD the allocation admits.  The dominant kernel k_eq_table<false, T> and the")
 out.append("# table builder k_base_tables<T> (T = teeth of the comb) run without scratch; round 1's single equation kernel (k_msm_jobs) had 159 VGPR spills / 480 B.")
+for row in rows:          # the small-batch verifier (latency_kernels.cuh): what the compiler reports, said in words
+    if "k_ballot_small" in row[0] and row[0] not in seen:
+        seen.add(row[0])
+        vgpr_spill, sgpr_spill, scratch = int(row[7]), int(row[6]), int(row[4])
+        what = "spills no VGPR" if vgpr_spill == 0 else f"SPILLS {vgpr_spill} VGPRs"
+        if scratch and vgpr_spill == 0:
+            what += f"; its {scratch} scratch bytes per lane are therefore stack arrays, not spills (k_hash, whose Merlin programs it inlines, has such arrays too)"
+        elif scratch == 0:
+            what += " and uses no scratch"
+        out.append(f"# {row[0]}: {row[5]} wave(s) per SIMD, {what}; {sgpr_spill} SGPR spills (to VGPR lanes).")
+seen = set()
 out.append(f"{'kernel':72s} {'SGPR':>5s} {'VGPR':>5s} {'AGPR':>5s} {'scratch':>8s} {'occ':>4s} {'sgpr_spill':>10s} {'vgpr_spill':>10s} {'LDS':>7s}")
 for row in rows:
     if row[0] in seen:
