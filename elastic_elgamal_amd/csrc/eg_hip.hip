@@ -291,6 +291,7 @@ struct Engine {
     hipEvent_t done = nullptr;
   } set[2];
   int n_sets = 2;
+  bool fused_tail = false;    // the stages end with k_encode_hash (engine_create)
   Knobs knobs;                 // the environment as the creation of this params object found it (read_knobs)
   uint8_t key_bytes[32] = {0}; // the election key as given (canonical encoding): two params objects belong to one election if these agree
   int teeth = 6;               // comb shape of the per-ballot tables (plan_teeth: 5 x 51 when a table serves two products, else 6 x 43)
@@ -562,6 +563,16 @@ static int engine_create(eg_ctx* ctx, eghost::Plan&& plan, const uint8_t pk[32],
   memcpy(e->key_bytes, pk, 32);
   if (e->knobs.teeth) e->teeth = e->knobs.teeth;     // measurement knob
   e->n_sets = e->knobs.streams;
+  // k_encode_hash (kernels.cuh) needs one thing of a stage: at most 16 deferred commitments, since it encodes those of TWO ballots in
+  // one batch of at most 32 (the bits of its zero_mask, the encw scratch rows).  It is switched on per PLAN, and more narrowly than the
+  // kernel needs, on purpose: only for ballot plans (the ones that tally) ALL of whose stages fit, which is single choice with up to 7
+  // options - the plans it was measured and tested on.  Multi-choice, quadratic voting and the proof plans (range, share, commitment
+  // equivalence), which have no tally, keep k_encode_batch + k_hash in every stage even where one stage would fit, so that their
+  // launches stay those of the profiles kept for them.  Within a fused plan a stage that defers nothing or hashes nothing (launch site
+  // in engine_verify_device) also takes the two-kernel path, which then launches only the kernel that has work.
+  e->fused_tail = !e->plan.tally_slots.empty();
+  for (auto& st : e->stages)
+    if (2 * st.defer_count > 32) e->fused_tail = false;
   // Two work sets whose kernels fill each other's launch tails (profiles/r03_ab_experiments.txt, blocks 3 and 9; M single-choice ballots/s):
   // with 6-tooth tables (57.6 KB per ballot and set) one set of 2^20 ballots 6.06, one set of 2^18 5.81 (-4 %), two sets of 2^18 6.05,
   // two sets of 2^19 6.13 (+1 %), two sets of 2^17 5.90; with the 5-tooth tables of the choice ballots (32.3 KB) two sets of 2^18 6.28,
@@ -790,6 +801,13 @@ static int engine_verify_device(Engine* e, size_t n, const void* d_ballots, void
       if (st.fam_count[FAM_ENCODE])
         hipLaunchKernelGGL(k_encode_plain, dim3(grid_for((size_t)st.fam_count[FAM_ENCODE] * cn, wide)), dim3(NT), 0, cs, B, e->d_jobs,
                            st.fam_first[FAM_ENCODE], st.fam_count[FAM_ENCODE]);
+      // the stage's tail in one launch: two ballots a lane, one inversion a pair
+      if (e->fused_tail && st.inst_count && st.defer_count) {
+        if (2 * st.defer_count > 32) return fail(EG_ERR_BAD_ARG, "internal: a stage of a fused plan defers more than 16 commitments");
+        hipLaunchKernelGGL(k_encode_hash, dim3(blocks_of(((size_t)cn + 1) / 2)), dim3(NT), 0, cs, B, e->d_defer_slots + st.defer_first,
+                           st.defer_count, e->d_insts, e->d_ops, st.inst_first, st.inst_count);
+        continue;
+      }
       for (int d0 = 0; d0 < st.defer_count; d0 += 32)   // one batched inversion per ballot and group of <= 32 commitments
         hipLaunchKernelGGL(k_encode_batch, dim3(grid_for(cn, wide)), dim3(NT), 0, cs, B, e->d_defer_slots + st.defer_first + d0,
                            std::min(32, st.defer_count - d0));

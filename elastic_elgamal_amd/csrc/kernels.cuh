@@ -14,6 +14,7 @@
 //   k_decode_points / k_check_scalars / k_derive_points   VALU (1 inverse square root per point)
 //   k_base_tables / k_eq_table / k_eq_generic   VALU-bound integer multiply-add: >90 % of the time
 //   k_hash         LDS + VALU (Keccak-f[1600])
+//   k_encode_hash  k_encode_batch + k_hash of a stage in one launch, two ballots a lane (single choice, up to 7 options)
 //   k_status, k_tally_*   trivial
 #pragma once
 #include <hip/hip_runtime.h>
@@ -388,15 +389,10 @@ __global__ void __launch_bounds__(NT, 2) k_encode_batch(EngineBufs B, const unsi
 }
 
 // ---- k_hash: Merlin transcript programs (proofs/mod.rs:39-57 + the per-proof label schedules) --------------------------------------
-__global__ void __launch_bounds__(NT) k_hash(EngineBufs B, const egplan::HashInst* insts, const egplan::HashOp* ops,
-                                             int inst_first, int n_insts) {
-  __shared__ u32 lds[50 * NT];
-  const size_t j = (size_t)blockIdx.x * NT + threadIdx.x;
-  if (j >= (size_t)n_insts * B.n) return;
-  const u32 b = (u32)(j % B.n);
-  const egplan::HashInst hi = insts[inst_first + (u32)(j / B.n)];
+// one transcript program of one ballot; the STROBE state is the lane's word-interleaved LDS column (LdsState)
+__device__ __forceinline__ void hash_program(const EngineBufs& B, u32 b, const egplan::HashInst hi, const egplan::HashOp* ops, u32* lds_col) {
   Transcript<LdsState> t;
-  t.st.base = lds + threadIdx.x;
+  t.st.base = lds_col;
   t.pos = 0; t.pos_begin = 0; t.cur_flags = 0;
 #pragma unroll 1
   for (u32 o = 0; o < hi.op_count; ++o) {
@@ -481,6 +477,66 @@ __global__ void __launch_bounds__(NT) k_hash(EngineBufs B, const egplan::HashIns
       }
       default: break;
     }
+  }
+}
+__global__ void __launch_bounds__(NT) k_hash(EngineBufs B, const egplan::HashInst* insts, const egplan::HashOp* ops,
+                                             int inst_first, int n_insts) {
+  __shared__ u32 lds[50 * NT];
+  const size_t j = (size_t)blockIdx.x * NT + threadIdx.x;
+  if (j >= (size_t)n_insts * B.n) return;
+  hash_program(B, (u32)(j % B.n), insts[inst_first + (u32)(j / B.n)], ops, lds + threadIdx.x);
+}
+
+// ---- k_encode_hash: the tail of a stage in one launch, two ballots a lane ------------------------------------------------------------
+// Lane j owns ballots j and j + ceil(n / 2) of the chunk (the last lane of an odd chunk owns one), so that every access stays
+// coalesced.  It encodes both ballots' deferred commitments as k_encode_batch does, but with ONE inversion for the pair (the chain is
+// 11 multiplications and 254 squarings whatever the batch holds), then runs the stage's transcript programs for both ballots as k_hash
+// does, one after the other on the lane's LDS column.  A commitment whose denominator vanishes is replaced by 1 in the product and
+// flagged, per element, so a degenerate commitment poisons neither its own ballot's other encodings nor its partner's.  The lane reads
+// back only encodings it wrote itself.  Needs 2 * n_slots <= 32 (the bits of zero_mask; the caller falls back to the two kernels).
+__global__ void __launch_bounds__(NT, 3) k_encode_hash(EngineBufs B, const unsigned short* slots, int n_slots, const egplan::HashInst* insts,
+                                                       const egplan::HashOp* ops, int inst_first, int n_insts) {
+  __shared__ u32 lds[50 * NT];
+  const u32 half = (B.n + 1u) / 2u;
+  const u32 j = blockIdx.x * NT + threadIdx.x;
+  if (j >= half) return;
+  const int nb = (j + half < B.n) ? 2 : 1;
+  fe prod; fe_1(prod);
+  u32 zero_mask = 0;
+#pragma unroll 1
+  for (int q = 0; q < nb * n_slots; ++q) {
+    const int k = q < n_slots ? q : q - n_slots;
+    const u32 b = q < n_slots ? j : j + half;
+    ge p;
+    load_pt(p, B.dpt, B.cap, slots[k], b);
+    fe n; bool zero;
+    ge_double_encode_prepare(n, zero, p);
+    zero_mask |= (zero ? 1u : 0u) << q;
+    encw_store(B.encw, B.cap, 2 * k, b, prod);         // prefix product before q
+    encw_store(B.encw, B.cap, 2 * k + 1, b, n);
+    fe t; fe_mul(t, prod, n); prod = t;
+  }
+  fe inv;
+  fe_invert(inv, prod);
+#pragma unroll 1
+  for (int q = nb * n_slots - 1; q >= 0; --q) {
+    const int k = q < n_slots ? q : q - n_slots;
+    const u32 b = q < n_slots ? j : j + half;
+    fe pre, n, inv_n, t;
+    encw_load(pre, B.encw, B.cap, 2 * k, b);
+    encw_load(n, B.encw, B.cap, 2 * k + 1, b);
+    fe_mul(inv_n, inv, pre);                            // 1 / N_q
+    fe_mul(t, inv, n); inv = t;                         // inverse of the prefix product before q
+    ge p;
+    load_pt(p, B.dpt, B.cap, slots[k], b);
+    u32 out[8];
+    ge_double_encode_finish(out, p, inv_n, ((zero_mask >> q) & 1u) != 0);
+    store32(B.cmp, B.cap, slots[k], b, out);
+  }
+#pragma unroll 1
+  for (int i = 0; i < nb * n_insts; ++i) {
+    const int k = i < n_insts ? i : i - n_insts;
+    hash_program(B, i < n_insts ? j : j + half, insts[inst_first + k], ops, lds + threadIdx.x);
   }
 }
 

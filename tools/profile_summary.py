@@ -99,7 +99,7 @@ for w in () if TRAFFIC_ONLY else WORKLOADS:
 
 # ---- PMC passes ----------------------------------------------------------------------------------------------------
 want = [f"eg::k_eq_table<{m}, {t}>" for m in ("false", "true") for t in (5, 6)] + ["eg::k_eq_direct"] + \
-       [f"eg::{k}<{t}>" for k in ("k_eq_generic", "k_base_tables", "k_sum_tables") for t in (5, 6)] + ["eg::k_encode_batch", "eg::k_decode_points", "eg::k_hash"]
+       [f"eg::{k}<{t}>" for k in ("k_eq_generic", "k_base_tables", "k_sum_tables") for t in (5, 6)] + ["eg::k_encode_batch", "eg::k_decode_points", "eg::k_hash", "eg::k_encode_hash"]
 text = [f"# rocprofv3 --pmc <counter> -- python3 bench.py --steps 1 --warmup 0 --workload W --no-cpu-baseline --no-host-inclusive --no-wire-ingest --no-isolated --ballots {PMC_BALLOTS}   (MI355X)",
         "# separate passes per counter (FETCH_SIZE, WRITE_SIZE; for the single-choice workload also two groups of SQ counters); values are",
         "# summed over the launches of the one step (its chunks x stages).  FETCH_SIZE/WRITE_SIZE are in KiB; on gfx950 FETCH_SIZE reports half the",
