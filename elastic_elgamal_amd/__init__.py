@@ -140,6 +140,11 @@ def _load() -> C.CDLL:
         "eg_dlog_table_create": (C.c_int, [vp, sz, C.POINTER(C.c_uint64), C.POINTER(vp)]),
         "eg_dlog_table_destroy": (None, [vp]),
         "eg_dlog_table_get": (C.c_int, [vp, sz, cp, C.POINTER(C.c_uint64), cp]),
+        "eg_dlog_solver_create": (C.c_int, [vp, C.c_int, C.POINTER(vp)]),
+        "eg_dlog_solver_destroy": (None, [vp]),
+        "eg_dlog_solver_solve": (C.c_int, [vp, sz, cp, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64), cp]),
+        "eg_dlog_solver_max_span": (C.c_uint64, [vp, sz]),
+        "eg_dlog_solver_table_bytes": (sz, [vp]),
         "eg_vartime_multi_mul_batch_device": (C.c_int, [vp, sz, sz, vp, vp, vp, vp, vp, vp, vp]),
         "eg_prepared_point_size": (sz, []),
         "eg_points_prepare_device": (C.c_int, [vp, sz, vp, vp, vp, vp]),

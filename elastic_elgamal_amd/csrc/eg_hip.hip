@@ -29,6 +29,7 @@
 #include "kernels.cuh"
 #include "latency_kernels.cuh"
 #include "pippenger.cuh"
+#include "dlog_kernels.cuh"
 
 using namespace eg;
 
@@ -1702,6 +1703,177 @@ int eg_dlog_table_get(const eg_dlog_table* t, size_t n, const uint8_t* elements,
     found[i] = it != t->map.end();
     values[i] = found[i] ? it->second : 0;
   }
+  return EG_OK;
+}
+
+// ---- bounded discrete logarithms (dlog_kernels.cuh; range arithmetic: dlog_host.hpp) ---------------------------------------------------
+// DiscreteLogTable::new(lo..hi).get(e) for ranges that no table holds: a baby table of 2^baby_bits multiples of [4]B in HBM, built once,
+// and giant steps over [lo, hi) in launches of at most LAUNCH_LANES lanes.  After every launch the host reads the candidate list and
+// confirms each candidate with the existing primitive ([m]G encoded, compared with the element's bytes); it stops once every element is
+// answered.  The solver owns its table and scratch - the context's per-lane workspace is not touched - and every call runs on the
+// context's stream under the context's lock, ending with a synchronisation like the primitive tier.
+struct eg_dlog_solver {
+  eg_ctx* ctx = nullptr;
+  int baby_bits = 0;
+  u32 slot_mask = 0, max_probe = 0, cand_cap = 0;
+  unsigned long long *d_slots = nullptr, *d_cand = nullptr;
+  u32 *d_consts = nullptr, *d_scratch = nullptr, *d_count = nullptr;   // d_count[0] = candidates of a launch, [1] = insertions past the probe bound
+  size_t scratch_lanes = 0;
+  void *d_block = nullptr;          // per-call buffers of one block of elements: encodings, prepared points, done flags
+  size_t block_cap = 0;
+};
+static void dlog_solver_free(eg_dlog_solver* s) {
+  if (!s) return;
+  for (void* p : {(void*)s->d_slots, (void*)s->d_cand, (void*)s->d_consts, (void*)s->d_scratch, (void*)s->d_count, s->d_block}) if (p) (void)hipFree(p);
+  delete s;
+}
+static int dlog_scratch(eg_dlog_solver* s, size_t lanes) {
+  lanes = (lanes + NT - 1) / NT * NT;
+  if (lanes <= s->scratch_lanes) return EG_OK;
+  HIPCHK(hipStreamSynchronize(s->ctx->stream));
+  if (s->d_scratch) (void)hipFree(s->d_scratch);
+  s->d_scratch = nullptr; s->scratch_lanes = 0;
+  HIPCHK(hipMalloc((void**)&s->d_scratch, (size_t)DLOG_RUN * DLOG_RUN_WORDS * lanes * sizeof(u32)));
+  s->scratch_lanes = lanes;
+  return EG_OK;
+}
+static void dlog_niels_words(u32 w[DLOG_RUN_WORDS], const ge& p) {
+  ge_niels n; ge_to_niels(n, p);
+  for (int j = 0; j < EG_NL; ++j) { w[j] = n.ypx.v[j]; w[EG_NL + j] = n.ymx.v[j]; w[2 * EG_NL + j] = n.xy2d.v[j]; }
+}
+int eg_dlog_solver_create(eg_ctx* c, int baby_bits, eg_dlog_solver** out) { EG_LOCK(c);
+  if (!c || !out) return fail(EG_ERR_BAD_ARG, "bad argument");
+  *out = nullptr;
+  if (baby_bits == 0) baby_bits = egdlog::BABY_BITS_DEFAULT;
+  if (baby_bits < egdlog::BABY_BITS_MIN || baby_bits > egdlog::BABY_BITS_MAX) return fail(EG_ERR_BAD_ARG, "baby_bits must be 0 (default) or in 8..28");
+  eg_dlog_solver* s = new eg_dlog_solver();
+  ScopeExit drop{[&] { if (s) dlog_solver_free(s); }};
+  s->ctx = c; s->baby_bits = baby_bits;
+  const size_t entries = (size_t)1 << baby_bits, n_slots = 2 * entries;
+  s->slot_mask = (u32)(n_slots - 1);
+  s->max_probe = (u32)std::min<size_t>(DLOG_MAX_PROBE, n_slots);
+  hipStream_t st = c->stream;
+  HIPCHK(hipMalloc((void**)&s->d_slots, n_slots * sizeof(unsigned long long)));
+  HIPCHK(hipMalloc((void**)&s->d_consts, 2 * DLOG_RUN_WORDS * sizeof(u32)));
+  HIPCHK(hipMalloc((void**)&s->d_count, 2 * sizeof(u32)));
+  HIPCHK(hipMemsetAsync(s->d_slots, 0, n_slots * sizeof(unsigned long long), st));
+  HIPCHK(hipMemsetAsync(s->d_count, 0, 2 * sizeof(u32), st));
+  // the two step points, on the host (the device headers compile for both sides): niels([4]B) and niels(-[4 W]B)
+  u32 consts[2 * DLOG_RUN_WORDS];
+  {
+    ge b4, t; ge_generator(t);
+    ge_dbl_full(b4, t); ge_dbl_full(t, b4); b4 = t;
+    dlog_niels_words(consts, b4);
+    ge w = b4;
+    for (int i = 0; i < baby_bits; ++i) { ge_dbl_full(t, w); w = t; }
+    ge_neg(t, w);
+    dlog_niels_words(consts + DLOG_RUN_WORDS, t);
+  }
+  TRY(h2d(s->d_consts, consts, sizeof(consts), st));
+  const size_t runs = entries / DLOG_RUN, per = std::min<size_t>(runs, egdlog::LAUNCH_LANES);
+  TRY(dlog_scratch(s, per));
+  for (size_t r0 = 0; r0 < runs; r0 += per) {
+    const size_t nr = std::min(per, runs - r0);
+    hipLaunchKernelGGL(k_dlog_baby, dim3(blocks_of(nr)), dim3(NT), 0, st, (u32)r0, (u32)nr, (u32)entries, c->tabG, s->d_consts, s->d_scratch,
+                       s->scratch_lanes, s->d_slots, s->slot_mask, s->max_probe, s->d_count + 1);
+  }
+  u32 over = 0;
+  TRY(d2h(&over, s->d_count + 1, sizeof(u32), st));
+  HIPCHK(hipStreamSynchronize(st));
+  HIPCHK(hipGetLastError());
+  if (over) return fail(EG_ERR_HIP, "internal: the baby table needed a probe sequence beyond its bound");
+  c->refs.fetch_add(1);   // dropped by eg_dlog_solver_destroy
+  *out = s; s = nullptr;
+  return EG_OK;
+}
+void eg_dlog_solver_destroy(eg_dlog_solver* s) {
+  if (!s) return;
+  eg_ctx* c = s->ctx;
+  {
+    EG_LOCK(c);
+    (void)hipStreamSynchronize(c->stream);
+    dlog_solver_free(s);
+  }
+  ctx_release(c);
+}
+uint64_t eg_dlog_solver_max_span(const eg_dlog_solver* s, size_t n) { return s ? egdlog::max_span(s->baby_bits, n) : 0; }
+size_t eg_dlog_solver_table_bytes(const eg_dlog_solver* s) { return s ? ((size_t)s->slot_mask + 1) * sizeof(unsigned long long) : 0; }
+int eg_dlog_solver_solve(eg_dlog_solver* s, size_t n, const uint8_t* elements, uint64_t lo, uint64_t hi, uint64_t* values, uint8_t* found) {
+  eg_ctx* c = s ? s->ctx : nullptr;
+  EG_LOCK(c);
+  if (!s || (n && (!elements || !values || !found))) return fail(EG_ERR_BAD_ARG, "bad argument");
+  egdlog::Range R;
+  const int rr = egdlog::plan_range(s->baby_bits, n, lo, hi, &R);
+  if (rr == egdlog::RANGE_REVERSED) return fail(EG_ERR_BAD_ARG, "lo > hi");
+  if (rr == egdlog::RANGE_TOO_WIDE)
+    return fail(EG_ERR_BAD_ARG, "hi - lo is wider than eg_dlog_solver_max_span for this many elements: raise baby_bits (or split the range)");
+  static const uint8_t zero[32] = {0};
+  for (size_t i = 0; i < n; ++i) { values[i] = 0; found[i] = memcmp(elements + 32 * i, zero, 32) == 0; }   // the identity is always 0
+  if (!n || !R.steps) return EG_OK;
+  hipStream_t st = c->stream;
+  const size_t eb = egdlog::block_elems(n);
+  if (eb > s->block_cap) {
+    HIPCHK(hipStreamSynchronize(st));
+    if (s->d_block) (void)hipFree(s->d_block);
+    s->d_block = nullptr; s->block_cap = 0;
+    HIPCHK(hipMalloc(&s->d_block, eb * (32 + PREP_WORDS * 4 + 1) + 64));
+    // candidates of ONE launch: an element has one true hit, the '-' reading of a hit is rare and a 32-bit tag collides once in 2^32
+    // probes, so four per element and a margin is far more than a launch produces; beyond it the call FAILS, it never drops a candidate
+    if (s->d_cand) (void)hipFree(s->d_cand);
+    s->d_cand = nullptr; s->cand_cap = 0;
+    const size_t cap = 4 * eb + 4096;
+    HIPCHK(hipMalloc((void**)&s->d_cand, cap * 2 * sizeof(unsigned long long)));
+    s->cand_cap = (u32)cap;
+    s->block_cap = eb;
+  }
+  u32* d_prep = (u32*)s->d_block;                                           // 96-byte records first: 16-byte aligned
+  u32* d_enc = (u32*)((char*)s->d_block + s->block_cap * PREP_WORDS * 4);
+  unsigned char* d_done = (unsigned char*)s->d_block + s->block_cap * (PREP_WORDS * 4 + 32);
+  std::vector<unsigned char> done;
+  std::vector<unsigned long long> cand;
+  for (size_t e0 = 0; e0 < n; e0 += eb) {
+    const size_t ne = std::min(eb, n - e0);
+    TRY(h2d(d_enc, elements + 32 * e0, ne * 32, st));
+    hipLaunchKernelGGL(k_prim_points_prepare, dim3(blocks_of(ne)), dim3(NT), 0, st, ne, (const u32*)d_enc, d_prep, d_done);
+    done.assign(ne, 0);
+    TRY(d2h(done.data(), d_done, ne, st));
+    HIPCHK(hipStreamSynchronize(st));
+    size_t open = 0;
+    for (size_t i = 0; i < ne; ++i) { done[i] = (!done[i] || found[e0 + i]) ? 1 : 0; open += !done[i]; }   // undecodable, or the identity
+    TRY(h2d(d_done, done.data(), ne, st));
+    const uint64_t per = egdlog::launch_runs(ne);
+    for (uint64_t r0 = 0; r0 < R.runs && open; r0 += per) {
+      const uint64_t nr = std::min<uint64_t>(per, R.runs - r0);
+      const size_t lanes = ne * (size_t)nr;
+      TRY(dlog_scratch(s, lanes));
+      HIPCHK(hipMemsetAsync(s->d_count, 0, sizeof(u32), st));
+      hipLaunchKernelGGL(k_dlog_giant, dim3(blocks_of(lanes)), dim3(NT), 0, st, (u32)e0, (u32)ne, (const u32*)d_prep, (const unsigned char*)d_done,
+                         (u64)lo, (u64)R.span, (u64)r0, (u32)nr, (u64)R.steps, s->baby_bits, c->tabG, s->d_consts, s->d_scratch, s->scratch_lanes,
+                         (const unsigned long long*)s->d_slots, s->slot_mask, s->max_probe, s->d_count, s->cand_cap, s->d_cand);
+      u32 cnt = 0;
+      TRY(d2h(&cnt, s->d_count, sizeof(u32), st));
+      HIPCHK(hipStreamSynchronize(st));
+      if (cnt > s->cand_cap) return fail(EG_ERR_HIP, "internal: more candidates in one launch than the list holds");
+      if (!cnt) continue;
+      cand.resize(2 * (size_t)cnt);
+      TRY(d2h(cand.data(), s->d_cand, cand.size() * sizeof(unsigned long long), st));
+      HIPCHK(hipStreamSynchronize(st));
+      // confirm: [m]G encoded against the element itself; a false candidate changes nothing and the search goes on
+      std::vector<uint8_t> sc(32 * (size_t)cnt, 0), enc(32 * (size_t)cnt);
+      for (u32 k = 0; k < cnt; ++k) memcpy(sc.data() + 32 * (size_t)k, &cand[2 * (size_t)k + 1], 8);
+      TRY(prim_msm(c, cnt, 0, nullptr, nullptr, sc.data(), enc.data(), nullptr));
+      bool changed = false;
+      for (u32 k = 0; k < cnt; ++k) {
+        const size_t e = (size_t)cand[2 * (size_t)k];
+        if (e < e0 || e >= e0 + ne || done[e - e0]) continue;
+        if (memcmp(enc.data() + 32 * (size_t)k, elements + 32 * e, 32) != 0) continue;
+        values[e] = cand[2 * (size_t)k + 1]; found[e] = 1; done[e - e0] = 1; --open; changed = true;
+      }
+      if (changed) TRY(h2d(d_done, done.data(), ne, st));
+    }
+    HIPCHK(hipStreamSynchronize(st));
+  }
+  HIPCHK(hipGetLastError());
   return EG_OK;
 }
 

@@ -209,6 +209,23 @@ typedef struct eg_dlog_table eg_dlog_table;
 int eg_dlog_table_create(eg_ctx*, size_t n, const uint64_t* values, eg_dlog_table** out);
 void eg_dlog_table_destroy(eg_dlog_table*);
 int eg_dlog_table_get(const eg_dlog_table*, size_t n, const uint8_t* elements /*32n*/, uint64_t* values, uint8_t* found);
+/* The same answers for ranges that no table can hold (10^7 .. 2^48 values): DiscreteLogTable::new(lo..hi).get(e) by baby-step/giant-step
+ * on the GPU (csrc/dlog_kernels.cuh).  A solver owns a table of 2^baby_bits multiples of the generator in device memory
+ * (eg_dlog_solver_table_bytes: 16 bytes per entry; 0 = the default width, 24), built once; it is independent of any range.
+ * eg_dlog_solver_solve answers n elements at once (n = the options of a tally): found[i] = 1 and values[i] = m iff some m in [lo, hi),
+ * m != 0, has serialize([m]G) == element i.  The identity (32 zero bytes) is always (0, found), whatever lo - the rule of the reference
+ * and of eg_dlog_table_get; an encoding that does not decode gives found = 0 and the call still returns EG_OK.  lo == hi is the empty
+ * range, lo > hi is EG_ERR_BAD_ARG, hi may be 2^64 - 1.  The answer is exact: every candidate of the search is confirmed against the
+ * element's bytes before it is reported.  A call takes time in proportion to n (hi - lo) / 2^baby_bits, so the span is bounded:
+ * hi - lo above eg_dlog_solver_max_span(solver, n) is EG_ERR_BAD_ARG (raise baby_bits, or split the range) - the widest call admitted
+ * takes about ten seconds.  Host pointers only; calls take the context's lock like every other entry. */
+typedef struct eg_dlog_solver eg_dlog_solver;
+int eg_dlog_solver_create(eg_ctx*, int baby_bits /* 0 = default; else 8..28 */, eg_dlog_solver** out);
+void eg_dlog_solver_destroy(eg_dlog_solver*);
+int eg_dlog_solver_solve(eg_dlog_solver*, size_t n, const uint8_t* elements /*32n*/, uint64_t lo, uint64_t hi, uint64_t* values,
+                         uint8_t* found);
+uint64_t eg_dlog_solver_max_span(const eg_dlog_solver*, size_t n); /* widest hi - lo a call with n elements accepts */
+size_t eg_dlog_solver_table_bytes(const eg_dlog_solver*);
 
 /* ---- batch tier: EncryptedChoice --------------------------------------------------------------------------------
  * wire layout of one ballot (stride = eg_choice_ballot_size):

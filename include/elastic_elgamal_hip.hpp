@@ -603,5 +603,28 @@ class DiscreteLogTable {
  private:
   eg_dlog_table* t_ = nullptr;
 };
+// DiscreteLogTable::new(lo..hi) for ranges no table can hold: baby-step/giant-step on the GPU (eg_dlog_solver_*).  One solver serves
+// any range; solve() answers every option of a tally in one call.
+class DiscreteLogSolver {
+ public:
+  explicit DiscreteLogSolver(const Context& ctx, int baby_bits = 0) { check(eg_dlog_solver_create(ctx.raw(), baby_bits, &s_)); }
+  ~DiscreteLogSolver() { eg_dlog_solver_destroy(s_); }
+  DiscreteLogSolver(const DiscreteLogSolver&) = delete;
+  DiscreteLogSolver& operator=(const DiscreteLogSolver&) = delete;
+  std::vector<std::optional<uint64_t>> solve(const std::vector<Element>& decrypted_elements, uint64_t lo, uint64_t hi) const {
+    Bytes in;
+    for (auto& e : decrypted_elements) in.insert(in.end(), e.begin(), e.end());
+    std::vector<uint64_t> v(decrypted_elements.size());
+    std::vector<uint8_t> found(decrypted_elements.size());
+    check(eg_dlog_solver_solve(s_, v.size(), in.data(), lo, hi, v.data(), found.data()));
+    std::vector<std::optional<uint64_t>> out;
+    for (size_t i = 0; i < v.size(); ++i) out.push_back(found[i] ? std::optional<uint64_t>(v[i]) : std::nullopt);
+    return out;
+  }
+  uint64_t max_span(size_t n) const { return eg_dlog_solver_max_span(s_, n); }
+  size_t table_bytes() const { return eg_dlog_solver_table_bytes(s_); }
+ private:
+  eg_dlog_solver* s_ = nullptr;
+};
 
 }  // namespace elastic_elgamal_hip
