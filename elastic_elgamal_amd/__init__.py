@@ -180,6 +180,12 @@ def _load() -> C.CDLL:
         "eg_qv_tally_reset_async": (C.c_int, [vp, vp]),
         "eg_qv_tally_encode_device": (C.c_int, [vp, vp, vp]),
         "eg_points_sum_device": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, vp]),
+        "eg_choice_tally_grouped_scratch_bytes": (sz, [vp, sz, C.c_uint32]),
+        "eg_choice_tally_grouped_device": (C.c_int, [vp, sz, vp, vp, vp, C.c_uint32, vp, vp, vp, vp, vp]),
+        "eg_choice_tally_grouped": (C.c_int, [vp, sz, vp, vp, vp, C.c_uint32, vp, vp]),
+        "eg_qv_tally_grouped_scratch_bytes": (sz, [vp, sz, C.c_uint32]),
+        "eg_qv_tally_grouped_device": (C.c_int, [vp, sz, vp, vp, vp, C.c_uint32, vp, vp, vp, vp, vp]),
+        "eg_qv_tally_grouped": (C.c_int, [vp, sz, vp, vp, vp, C.c_uint32, vp, vp]),
         "eg_proof_params_create": (C.c_int, [vp, cp, C.c_int, C.c_uint64, C.POINTER(vp)]),
         "eg_share_params_create": (C.c_int, [vp, cp, C.c_uint64, C.c_uint64, C.c_uint64, cp, C.POINTER(vp)]),
         "eg_proof_params_destroy": (None, [vp]),
@@ -243,6 +249,8 @@ def _load() -> C.CDLL:
 PACK_RESHAPE = 0xFFFFFFFE
 ABI_VERSION = 7          # include/eg_hip.h: EG_ABI_VERSION
 SMALL_BATCH_MAX = 4096   # include/eg_hip.h: EG_SMALL_BATCH_MAX, the most ballots one verify_small call takes
+GROUP_NONE = 0xFFFFFFFF          # include/eg_hip.h: EG_GROUP_NONE, the group id that leaves a ballot out of every group
+TALLY_GROUPS_MAX = 1 << 24       # include/eg_hip.h: EG_TALLY_GROUPS_MAX
 
 
 def pack_json(text, n_options: int, single: bool | None = None, credits: int | None = None, threads: int = 0, max_objects: int = 0):
@@ -832,6 +840,42 @@ class _BatchParams:
         out = C.create_string_buffer(64 * self.n_options)
         _check(self._fn("tally_encode")(self._h, out))
         return out.raw
+
+    def tally_grouped_scratch_bytes(self, n: int, n_groups: int) -> int:
+        """Device scratch that tally_grouped_device needs for n ballots in n_groups groups (0 for arguments it refuses)."""
+        return int(self._fn("tally_grouped_scratch_bytes")(self._h, n, n_groups))
+
+    def tally_grouped(self, ballots: bytes, status, groups, n_groups: int):
+        """Per-group tally of the accepted ballots of a verified batch (eg_*_tally_grouped): `status` = the words a verify entry wrote
+        for `ballots`, `groups` = one group id per ballot (GROUP_NONE: in no group).  Returns (tallies, counts): tallies = n_groups x
+        n_options x 64 bytes, tallies[g] what tally_encode() would give after verifying only group g's ballots; counts[g] = accepted
+        ballots of group g.  Stateless: the running tally is not touched.  An accepted ballot with an id out of range, or with a
+        tally point that does not decode, fails the call (EG_ERR_BAD_ARG)."""
+        n = len(ballots) // self.ballot_size
+        if n * self.ballot_size != len(ballots):
+            raise ValueError("ballots is not a whole number of packed ballots")
+        status, groups = list(status), list(groups)
+        if len(status) != n or len(groups) != n:
+            raise ValueError("status and groups need one word per ballot")
+        st = (C.c_uint32 * max(n, 1))(*status)
+        gr = (C.c_uint32 * max(n, 1))(*groups)
+        buf = (C.c_char * max(len(ballots), 1)).from_buffer_copy(ballots or b"\0")
+        ng = max(int(n_groups), 0)
+        if not 0 < ng <= TALLY_GROUPS_MAX:                     # refused by the library: no output buffers of that size are made
+            _check(self._fn("tally_grouped")(self._h, n, buf, st, gr, ng & 0xFFFFFFFF, None, None))
+            raise EgError("eg_*_tally_grouped accepted a group count it must refuse")
+        tallies = C.create_string_buffer(ng * 64 * self.n_options)
+        counts = (C.c_uint32 * ng)()
+        _check(self._fn("tally_grouped")(self._h, n, buf, st, gr, ng, tallies, counts))
+        return tallies.raw, list(counts)
+
+    def tally_grouped_device(self, n: int, d_ballots: int, d_status: int, d_groups: int, n_groups: int, d_scratch: int, d_tallies: int,
+                             d_bad: int, d_counts: int = 0, stream: int = 0):
+        """Asynchronous device-pointer variant (eg_*_tally_grouped_device): no allocation, no host synchronisation.  d_scratch:
+        tally_grouped_scratch_bytes(n, n_groups) bytes; d_bad: two uint32 the library writes (ids out of range, undecodable points) -
+        the caller must read them and discard the tallies if either is non-zero."""
+        _check(self._fn("tally_grouped_device")(self._h, n, d_ballots or None, d_status or None, d_groups or None, n_groups,
+                                                 d_scratch or None, d_tallies or None, d_counts or None, d_bad or None, stream or None))
 
 
 class ChoiceParams(_BatchParams):

@@ -30,6 +30,7 @@
 #include "latency_kernels.cuh"
 #include "pippenger.cuh"
 #include "dlog_kernels.cuh"
+#include "group_tally_kernels.cuh"
 
 using namespace eg;
 
@@ -256,6 +257,7 @@ struct Engine {
   egplan::HashOp* d_ops = nullptr;
   egplan::StatusRule* d_rules = nullptr;
   u32* d_tally_slots = nullptr;
+  u32* d_tally_items = nullptr;                // wire item behind every tally slot (group_tally_host.hpp: tally_items): what the per-group tally reads
   unsigned short* d_base_slots = nullptr;      // FlatPlan::build_slots: point slots by the stage that builds their tables
   egplan::SumBase* d_sum_bases = nullptr;      // FlatPlan::sums / sum_members (members as table slots)
   unsigned short* d_sum_members = nullptr;
@@ -362,7 +364,7 @@ static int gen_workspace(Engine* e, size_t n, unsigned words, int* blocks_out) {
 static void engine_free(Engine* e) {
   if (!e) return;
   void* ptrs[] = {e->d_pt_items, e->d_sc_items, e->d_dclasses, e->d_dterms, e->d_jobs, e->d_vterms, e->d_insts, e->d_ops,
-                  e->d_rules, e->d_tally_slots, e->d_base_slots, e->d_sum_bases, e->d_sum_members, e->d_acc_sums, e->d_acc_members, e->d_defer_slots, e->d_blob, e->d_cpts, e->d_prefixes, e->d_key_words,
+                  e->d_rules, e->d_tally_slots, e->d_tally_items, e->d_base_slots, e->d_sum_bases, e->d_sum_members, e->d_acc_sums, e->d_acc_members, e->d_defer_slots, e->d_blob, e->d_cpts, e->d_prefixes, e->d_key_words,
                   e->tally_saved, e->tally_saved2, e->tally_saved3, e->d_tally_enc, e->d_wire, e->d_status, e->gen_ws, e->d_gen_desc, e->d_h_srcs, e->d_h_words,
                   e->d_small_stages, e->d_small_levels, e->small_ws};
   for (void* p : ptrs) if (p) (void)hipFree(p);
@@ -504,6 +506,11 @@ static int engine_create(eg_ctx* ctx, eghost::Plan&& plan, const uint8_t pk[32],
   if ((rc = upload(&e->d_ops, ops, s))) return rc;
   if ((rc = upload(&e->d_rules, P.rules, s))) return rc;
   if ((rc = upload(&e->d_tally_slots, P.tally_slots, s))) return rc;
+  {
+    const std::vector<uint32_t> items = eggt::tally_items(P.pt_items, P.tally_slots);
+    for (uint32_t it : items) if (it == 0xffffffffu) return fail(EG_ERR_BAD_ARG, "internal: a tally slot of the plan is not a wire point");
+    if ((rc = upload(&e->d_tally_items, items, s))) return rc;
+  }
   if ((rc = upload(&e->d_base_slots, F.build_slots, s))) return rc;
   if ((rc = upload(&e->d_sum_bases, F.sums, s))) return rc;
   if ((rc = upload(&e->d_sum_members, F.sum_members, s))) return rc;
@@ -1932,6 +1939,126 @@ int eg_points_sum_device(eg_ctx* c, int n_ranks, int n_points, const void* d_in,
                      (u32*)d_bad);
   HIPCHK(hipGetLastError());
   return EG_OK;
+}
+// ---- per-group tally of a verified batch (group_tally_kernels.cuh) ---------------------------------------------------------------------
+// Reads the engine's immutable plan data only (stride, the tally items uploaded at creation): no lock, no workspace, no running tally.
+static size_t grouped_scratch_bytes(const Engine* e, size_t n, uint32_t n_groups) {
+  if (!e || eggt::refuse(n, n_groups)) return 0;
+  return eggt::layout(n, n_groups, (uint32_t)e->plan.tally_slots.size()).total;
+}
+static int grouped_check(const Engine* e, size_t n, uint32_t n_groups) {
+  if (const char* why = eggt::refuse(n, n_groups)) return fail(EG_ERR_BAD_ARG, std::string("grouped tally: ") + why);
+  if (!e) return fail(EG_ERR_BAD_ARG, "grouped tally: null params");
+  return EG_OK;
+}
+static int grouped_launch(Engine* e, size_t n, const void* d_ballots, const void* d_status, const void* d_groups, uint32_t n_groups,
+                          void* d_scratch, void* d_tallies, void* d_counts, void* d_bad, hipStream_t s) {
+  TRY_(grouped_check(e, n, n_groups));
+  if (n && (!d_ballots || !d_status || !d_groups || !d_tallies || !d_bad)) return fail(EG_ERR_BAD_ARG, "grouped tally: null device pointer");
+  if (!d_tallies) return EG_OK;                                          // n == 0 and nowhere to write the zero tallies to
+  const u32 T = (u32)e->plan.tally_slots.size();
+  const eggt::Layout L = eggt::layout(n, n_groups, T);
+  if (L.total && !d_scratch) return fail(EG_ERR_BAD_ARG, "grouped tally: null scratch (eg_*_tally_grouped_scratch_bytes says how much)");
+  if (((uintptr_t)d_ballots | (uintptr_t)d_scratch) & 15u) return fail(EG_ERR_BAD_ARG, "grouped tally: ballots and scratch must be 16-byte aligned");
+  if (((uintptr_t)d_status | (uintptr_t)d_groups | (uintptr_t)d_tallies | (uintptr_t)d_counts | (uintptr_t)d_bad) & 3u)
+    return fail(EG_ERR_BAD_ARG, "grouped tally: misaligned device pointer");
+  if (L.n_levels > eggt::MAX_LEVELS) return fail(EG_ERR_BAD_ARG, "grouped tally: too many ballots");
+  HIPCHK(hipSetDevice(e->ctx->device));
+  char* base = static_cast<char*>(d_scratch);
+  auto at = [&](size_t o) { return reinterpret_cast<u32*>(base + o); };
+  u32 *counts = at(L.counts), *cursors = at(L.cursors), *offsets = at(L.offsets), *totals = at(L.totals), *idx = at(L.idx);
+  uint4* psum[2] = {reinterpret_cast<uint4*>(base + L.psum[0]), reinterpret_cast<uint4*>(base + L.psum[1])};
+  const u32* status = static_cast<const u32*>(d_status);
+  const u32* groups = static_cast<const u32*>(d_groups);
+  u32* bad = static_cast<u32*>(d_bad);
+  const int cap = e->ctx->cus * 64;
+  if (bad) HIPCHK(hipMemsetAsync(bad, 0, 2 * sizeof(u32), s));
+  HIPCHK(hipMemsetAsync(counts, 0, L.offsets - L.counts, s));          // counts and cursors
+  if (n) hipLaunchKernelGGL(k_gt_count, dim3(blocks_of(n)), dim3(NT), 0, s, (u32)n, status, groups, n_groups, counts, bad);
+  GtScan S;
+  S.offsets = offsets; S.totals = totals; S.tile_sums = at(L.tiles);
+  for (int l = 0; l < eggt::MAX_LEVELS; ++l) { S.pieces[l] = at(L.pieces[l]); S.piece0[l] = at(L.piece0[l]); }
+  hipLaunchKernelGGL(k_gt_scan_tiles, dim3(L.n_tiles), dim3(NT), 0, s, (const u32*)counts, n_groups, L.n_levels, eggt::S1, eggt::S2, S);
+  hipLaunchKernelGGL(k_gt_scan_tops, dim3(1), dim3(64 * GT_SEQ), 0, s, L.n_tiles, S);
+  hipLaunchKernelGGL(k_gt_scan_apply, dim3(L.n_tiles), dim3(NT), 0, s, (const u32*)counts, n_groups, L.n_levels, eggt::S1, eggt::S2, S);
+  const u32 *cnt = counts, *off = offsets;
+  if (n) {
+    hipLaunchKernelGGL(k_gt_fill, dim3(blocks_of(n)), dim3(NT), 0, s, (u32)n, status, groups, n_groups, (const u32*)offsets, cursors, idx);
+    // level 0: pieces of the ballot lists, summed from the wire; levels 1 ..: pieces of the partial sums of the level before
+    for (int l = 0; l < L.n_levels; ++l) {
+      const GtLevel lv{cnt, off, S.piece0[l]};
+      const int grid = grid_for(L.psum_points[l & 1] * T, cap);          // (levels >= 2 have no more pieces than the level two before)
+      if (l == 0)
+        hipLaunchKernelGGL(k_gt_sum_wire, dim3(grid), dim3(NT), 0, s, eggt::S1, T, lv, (const u32*)(totals + l), n_groups, (const u32*)idx,
+                           GtWireDev{static_cast<const u32*>(d_ballots), (u32)(e->plan.stride / 4), (u32)n}, (const u32*)e->d_tally_items, psum[0], bad);
+      else
+        hipLaunchKernelGGL(k_gt_sum_points, dim3(grid), dim3(NT), 0, s, eggt::S2, T, lv, (const u32*)(totals + l), n_groups,
+                           (const uint4*)psum[(l - 1) & 1], psum[l & 1]);
+      cnt = S.pieces[l]; off = S.piece0[l];
+    }
+  }
+  const int last = L.n_levels - 1;
+  hipLaunchKernelGGL(k_gt_encode, dim3(grid_for((size_t)n_groups * T, cap)), dim3(NT), 0, s, n_groups, T, (const u32*)S.pieces[last],
+                     (const u32*)S.piece0[last], (const uint4*)psum[last & 1], (const u32*)counts, static_cast<u32*>(d_tallies),
+                     static_cast<u32*>(d_counts));
+  HIPCHK(hipGetLastError());
+  return EG_OK;
+}
+// host buffers: stages everything in device memory of its own, runs the pass on a stream of its own and waits for it
+static int grouped_host(Engine* e, size_t n, const uint8_t* ballots, const uint32_t* status, const uint32_t* groups, uint32_t n_groups,
+                        uint8_t* tallies, uint32_t* counts) {
+  TRY_(grouped_check(e, n, n_groups));
+  if (!tallies || (n && (!ballots || !status || !groups))) return fail(EG_ERR_BAD_ARG, "grouped tally: null pointer");
+  HIPCHK(hipSetDevice(e->ctx->device));
+  const size_t T = e->plan.tally_slots.size(), stride = e->plan.stride;
+  const size_t sizes[6] = {n * stride, n * 4, n * 4, grouped_scratch_bytes(e, n, n_groups), (size_t)n_groups * T * 32, (size_t)n_groups * 4 + 8};
+  void* d[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  hipStream_t s = nullptr;
+  ScopeExit release{[&]() {
+    for (void* p : d) if (p) (void)hipFree(p);
+    if (s) (void)hipStreamDestroy(s);
+  }};
+  for (int k = 0; k < 6; ++k) {
+    const hipError_t he = hipMalloc(&d[k], std::max<size_t>(sizes[k], 16));
+    if (he == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(EG_ERR_NOMEM, "grouped tally: the staging buffers do not fit the device memory"); }
+    HIPCHK(he);
+  }
+  HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+  if (n) {
+    HIPCHK(hipMemcpyAsync(d[0], ballots, sizes[0], hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d[1], status, sizes[1], hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d[2], groups, sizes[2], hipMemcpyHostToDevice, s));
+  }
+  u32* d_counts = static_cast<u32*>(d[5]);
+  u32* d_bad = d_counts + n_groups;
+  TRY_(grouped_launch(e, n, d[0], d[1], d[2], n_groups, d[3], d[4], d_counts, d_bad, s));
+  u32 bad[2] = {0, 0};
+  HIPCHK(hipMemcpyAsync(tallies, d[4], sizes[4], hipMemcpyDeviceToHost, s));
+  if (counts) HIPCHK(hipMemcpyAsync(counts, d_counts, (size_t)n_groups * 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(bad, d_bad, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  if (bad[0] || bad[1])
+    return fail(EG_ERR_BAD_ARG, "grouped tally: " + std::to_string(bad[0]) + " accepted ballot(s) with a group id out of range, " +
+                                    std::to_string(bad[1]) + " tally point(s) of accepted ballots that do not decode: discard the tallies");
+  return EG_OK;
+}
+size_t eg_choice_tally_grouped_scratch_bytes(const eg_choice_params* p, size_t n, uint32_t n_groups) { return grouped_scratch_bytes(p ? p->eng : nullptr, n, n_groups); }
+size_t eg_qv_tally_grouped_scratch_bytes(const eg_qv_params* p, size_t n, uint32_t n_groups) { return grouped_scratch_bytes(p ? p->eng : nullptr, n, n_groups); }
+int eg_choice_tally_grouped_device(eg_choice_params* p, size_t n, const void* d_ballots, const void* d_status, const void* d_groups, uint32_t n_groups,
+                                   void* d_scratch, void* d_tallies, void* d_counts, void* d_bad, void* stream) {
+  return grouped_launch(p ? p->eng : nullptr, n, d_ballots, d_status, d_groups, n_groups, d_scratch, d_tallies, d_counts, d_bad, (hipStream_t)stream);
+}
+int eg_qv_tally_grouped_device(eg_qv_params* p, size_t n, const void* d_ballots, const void* d_status, const void* d_groups, uint32_t n_groups,
+                               void* d_scratch, void* d_tallies, void* d_counts, void* d_bad, void* stream) {
+  return grouped_launch(p ? p->eng : nullptr, n, d_ballots, d_status, d_groups, n_groups, d_scratch, d_tallies, d_counts, d_bad, (hipStream_t)stream);
+}
+int eg_choice_tally_grouped(eg_choice_params* p, size_t n, const uint8_t* ballots, const uint32_t* status, const uint32_t* groups, uint32_t n_groups,
+                            uint8_t* tallies, uint32_t* counts) {
+  return grouped_host(p ? p->eng : nullptr, n, ballots, status, groups, n_groups, tallies, counts);
+}
+int eg_qv_tally_grouped(eg_qv_params* p, size_t n, const uint8_t* ballots, const uint32_t* status, const uint32_t* groups, uint32_t n_groups,
+                        uint8_t* tallies, uint32_t* counts) {
+  return grouped_host(p ? p->eng : nullptr, n, ballots, status, groups, n_groups, tallies, counts);
 }
 // builds the wide comb tables now (synchronously, ~12 GB each for G and K) instead of inside the first large verify call
 static int prepare_wide(Engine* e) {

@@ -1,6 +1,7 @@
 // voting.cpp -- the reference's examples/voting.rs on the GPU backend, in C++ on top of the C ABI:
 //   `Args::vote`            (examples/voting.rs:179-213)  ./voting [votes] [options] [seed]
 //   `Args::quadratic_vote`  (examples/voting.rs:219-269)  ./voting --qv [votes] [options] [credits] [seed]
+//   options: --devices N, --json, --precincts P
 // talliers' key -> voters create ballots from their own choices -> verify every ballot -> homomorphic totals -> decrypt and
 // compare with the EXPECTED totals the voters' choices add up to.  Threshold sharing of the key (examples/voting.rs:105-120) is out
 // of scope; a single key pair stands in for the shared key (tests/test_gpu_parity.py::test_threshold_tally_end_to_end
@@ -8,6 +9,8 @@
 // (eg_verify_*_batch_multi) over N contexts on the visible GPUs (all on GPU 0 when fewer are visible).  With --json the ballots travel
 // the way examples/voting.rs:195-198 prints them - serde_json text, ONE BALLOT AT A TIME - into the streaming entry
 // (JsonStream = eg_verify_choice_json_begin / eg_verify_json_feed / _end), which cuts, packs and verifies them as they arrive.
+// With --precincts P voter v belongs to precinct v mod P: after the overall totals, the per-precinct totals of the same verified batch
+// (tally_grouped = eg_*_tally_grouped, one pass over the accepted ballots) are decrypted the same way and must add up to the overall result.
 //
 //   g++ -std=c++17 -Iinclude examples/voting.cpp -Lelastic_elgamal_amd -leg_hip -Wl,-rpath,$PWD/elastic_elgamal_amd -o voting
 #include <cstdio>
@@ -31,7 +34,7 @@ struct Rng {
 // Self::tally (examples/voting.rs:122-177) with one key: decrypt each total = blinded - [sk]random, look it up in
 // DiscreteLogTable::new(0..=max), compare with the expected totals
 static bool tally(const Context& ctx, const Ristretto& group, const Scalar& sk, const std::vector<Ciphertext>& totals,
-                  const std::vector<uint64_t>& expected, uint64_t max_value) {
+                  const std::vector<uint64_t>& expected, uint64_t max_value, std::vector<uint64_t>* decrypted = nullptr) {
   std::vector<uint64_t> range(max_value + 1);
   for (uint64_t m = 0; m <= max_value; ++m) range[m] = m;
   const DiscreteLogTable lookup(ctx, range);
@@ -43,7 +46,33 @@ static bool tally(const Context& ctx, const Ristretto& group, const Scalar& sk, 
     if (!found) { printf("  variant #%zu: decryption failed\n", k + 1); return false; }
     printf("  variant #%zu decrypted tally: %llu (expected %llu)\n", k + 1, (unsigned long long)*found, (unsigned long long)expected[k]);
     ok = ok && *found == expected[k];
+    if (decrypted) decrypted->push_back(*found);
   }
+  return ok;
+}
+
+// --precincts: the totals of every precinct from the batch that was just verified, decrypted like the overall totals; they must equal
+// what the precinct's voters chose and add up to the overall result
+template <class Params, class Verdict>
+static bool precinct_tally(const Context& ctx, const Ristretto& group, const Scalar& sk, const Params& params, const Bytes& ballots,
+                           const Verdict& verdict, uint32_t precincts, const std::vector<std::vector<uint64_t>>& expected_by_precinct,
+                           const std::vector<uint64_t>& expected, uint64_t max_value) {
+  const size_t votes = verdict.results.size();
+  std::vector<uint32_t> status(votes), groups(votes);
+  for (size_t v = 0; v < votes; ++v) { status[v] = verdict.results[v] ? 1u : 0u; groups[v] = (uint32_t)(v % precincts); }
+  const GroupedTally by = params.tally_grouped(ballots, status, groups, precincts);
+  std::vector<uint64_t> sum(expected.size(), 0);
+  size_t accepted = 0;
+  bool ok = true;
+  for (uint32_t p = 0; p < precincts; ++p) {
+    printf("precinct #%u: %u accepted ballots\n", p + 1, by.accepted[p]);
+    std::vector<uint64_t> got;
+    ok = tally(ctx, group, sk, by.totals[p], expected_by_precinct[p], max_value, &got) && ok;
+    for (size_t k = 0; k < got.size() && k < sum.size(); ++k) sum[k] += got[k];
+    accepted += by.accepted[p];
+  }
+  ok = ok && sum == expected && accepted == verdict.accepted();
+  printf("precinct totals %s the overall totals\n", ok ? "add up to" : "DO NOT add up to");
   return ok;
 }
 
@@ -74,17 +103,20 @@ static std::string choice_to_json(const uint8_t* b, size_t options) {
 int main(int argc, char** argv) {
   bool qv = false, json = false;
   int devices = 1;
+  long precincts = 0;
   std::vector<std::string> pos;
   for (int i = 1; i < argc; ++i) {
     if (!strcmp(argv[i], "--qv")) qv = true;
     else if (!strcmp(argv[i], "--json")) json = true;
     else if (!strcmp(argv[i], "--devices") && i + 1 < argc) devices = atoi(argv[++i]);
+    else if (!strcmp(argv[i], "--precincts") && i + 1 < argc) precincts = atol(argv[++i]);
     else pos.push_back(argv[i]);
   }
   auto arg = [&](size_t k, uint64_t dflt) { return k < pos.size() ? strtoull(pos[k].c_str(), nullptr, 10) : dflt; };
   const size_t votes = (size_t)arg(0, 1000), options = (size_t)arg(1, 5);
   const uint64_t credits = qv ? arg(2, 20) : 0, seed = arg(qv ? 3 : 2, 1);
   if (devices < 1 || devices > 16) { printf("--devices must be in 1..16\n"); return 2; }
+  if (precincts < 0 || precincts > (long)EG_TALLY_GROUPS_MAX) { printf("--precincts must be in 0..%u\n", EG_TALLY_GROUPS_MAX); return 2; }
 
   // one context per device slot; slot d uses GPU d when the process sees that many, else GPU 0
   std::vector<std::unique_ptr<Context>> ctxs;
@@ -102,6 +134,7 @@ int main(int argc, char** argv) {
   const Element pk = group.mul_generator(sk);
   Rng rng{seed ^ 0xC0FFEEull};
   std::vector<uint64_t> expected(options, 0);
+  std::vector<std::vector<uint64_t>> expected_by_precinct((size_t)precincts, std::vector<uint64_t>(options, 0));
   bool ok = true;
 
   if (!qv) {
@@ -113,6 +146,7 @@ int main(int argc, char** argv) {
     const size_t forged = votes > 3 ? 3 : votes;                                       // one forged ballot must be rejected
     if (forged < votes) ballots[forged * params[0]->ballot_size() + 64 * options + 40] ^= 1;
     for (size_t i = 0; i < votes; ++i) if (i != forged) expected[choices[i]] += 1;
+    for (size_t i = 0; precincts && i < votes; ++i) if (i != forged) expected_by_precinct[i % precincts][choices[i]] += 1;
     std::vector<const ChoiceParams*> per;
     for (auto& p : params) per.push_back(p.get());
     BatchVerdict<ChoiceVerificationError> verdict;
@@ -138,6 +172,7 @@ int main(int argc, char** argv) {
     for (size_t i = 0; i < verdict.results.size(); ++i)
       if (verdict.results[i]) printf("  voter #%zu rejected: %s\n", i + 1, verdict.results[i]->to_string().c_str());
     ok = verdict.accepted() == votes - (forged < votes ? 1 : 0) && tally(ctx, group, sk, verdict.totals, expected, votes);
+    if (precincts) ok = precinct_tally(ctx, group, sk, *params[0], ballots, verdict, (uint32_t)precincts, expected_by_precinct, expected, votes) && ok;
   } else {
     std::vector<std::unique_ptr<QuadraticVotingParams>> params;
     for (auto& c : ctxs) params.push_back(std::make_unique<QuadraticVotingParams>(*c, pk, options, credits));
@@ -157,6 +192,8 @@ int main(int argc, char** argv) {
     const size_t forged = votes > 3 ? 3 : votes;
     if (forged < votes) ballots[forged * params[0]->ballot_size() + params[0]->ballot_size() - 40] ^= 1;
     for (size_t i = 0; i < votes; ++i) if (i != forged) for (size_t k = 0; k < options; ++k) expected[k] += all[i * options + k];
+    for (size_t i = 0; precincts && i < votes; ++i)
+      if (i != forged) for (size_t k = 0; k < options; ++k) expected_by_precinct[i % precincts][k] += all[i * options + k];
     std::vector<const QuadraticVotingParams*> per;
     for (auto& p : params) per.push_back(p.get());
     auto verdict = devices > 1 ? verify_batch_multi(per, ballots) : params[0]->verify_batch(ballots);   // encrypted.verify(&vote_params)
@@ -165,6 +202,7 @@ int main(int argc, char** argv) {
       if (verdict.results[i]) printf("  voter #%zu rejected (error kind %d)\n", i + 1, (int)verdict.results[i]->kind);
     const uint64_t max_votes = votes * params[0]->max_votes();                          // votes_count * vote_params.max_votes()
     ok = verdict.accepted() == votes - (forged < votes ? 1 : 0) && tally(ctx, group, sk, verdict.totals, expected, max_votes);
+    if (precincts) ok = precinct_tally(ctx, group, sk, *params[0], ballots, verdict, (uint32_t)precincts, expected_by_precinct, expected, max_votes) && ok;
   }
   printf("%s: the decrypted totals %s the expected ones\n", ok ? "OK" : "MISMATCH", ok ? "equal" : "differ from");
   return ok ? 0 : 1;

@@ -306,6 +306,48 @@ int eg_verify_choice_small_device(eg_choice_params*, size_t n, const void* d_bal
 int eg_verify_qv_small(eg_qv_params*, size_t n, const uint8_t* ballots, uint32_t* status, uint8_t* tally_out);
 int eg_verify_qv_small_device(eg_qv_params*, size_t n, const void* d_ballots, void* d_status, void* stream);
 
+/* ---- per-group tally: the accepted ballots of a verified batch, summed by precinct / district / ballot box in one pass ------------
+ * The verify entries add every accepted ballot into ONE tally (examples/voting.rs:199-203); an election that publishes results per
+ * precinct needs one tally per precinct.  These entries run AFTER a verify entry, over the same packed ballots and the status words it
+ * wrote: tallies[g] (n_options x 64 bytes, R || B per option, canonical encodings) is what eg_*_tally_encode would give after verifying
+ * only the ballots with groups[b] == g - the sum over the ballots with status[b] == 0 - and 64 zero bytes per option (Ciphertext::zero())
+ * for a group without an accepted ballot; counts[g] (optional) = accepted ballots of group g.  groups[b] == EG_GROUP_NONE leaves ballot b
+ * out of every group (the spoiled pile, another election's ballots).  Only the ciphertext points are needed, and they are decoded again
+ * from the wire bytes (2 n_options decodings per accepted ballot), so the pass is STATELESS: it reads nothing of the params object but its
+ * immutable plan, touches no running tally and no workspace, takes no lock, and may run from any thread and on any stream beside verify
+ * calls and open JSON streams of the same params object.  The same verified batch may be tallied again under another grouping
+ * (precinct, then county) without verifying again.  Results do not depend on the order of the ballots.
+ *
+ * UNTRUSTED INPUTS.  Every group id is bounds-checked before it indexes anything.  The library WRITES the two words of `bad` (it does
+ * not add to them): bad[0] = accepted ballots whose id is >= n_groups and not EG_GROUP_NONE (left out of every group); bad[1] = tally
+ * points of accepted ballots that do not decode - the status words were forged or belong to other ballots; such a point contributes the
+ * identity, as in eg_points_sum_device.  If either is non-zero the tallies are to be discarded; the host form then returns
+ * EG_ERR_BAD_ARG.  Ids and points of REJECTED ballots are never looked at.
+ * EG_ERR_BAD_ARG before anything is launched: n_groups == 0 or above EG_TALLY_GROUPS_MAX, n >= 2^31, a NULL d_ballots / d_status /
+ * d_groups / d_tallies / d_bad with n > 0, a NULL scratch pointer when the scratch size is not 0, ballots or scratch that are not
+ * 16-byte aligned.  n == 0 is valid: all-zero tallies.
+ *
+ * The `_device` form is asynchronous on `stream`, allocates nothing and never synchronises with the host; d_scratch is the caller's,
+ * eg_*_tally_grouped_scratch_bytes(params, n, n_groups) bytes (the convention of eg_msm_scratch_bytes_ctx; 0 for arguments that would be
+ * refused): 4 bytes per ballot, ~36 per group and the partial sums, 144 bytes x 2 n_options x (n / 32 + min(n, n_groups)) and a
+ * thirty-second of that again.  The host form stages its buffers in device memory of its own and returns when the results are written.
+ * MERGING.  Grouped tallies of several calls, slabs or ranks are merged with eg_points_sum_device(ctx, n_parts, n_groups * 2 *
+ * n_options, ...), counts by plain addition: no new collective. */
+#define EG_GROUP_NONE 0xffffffffu
+#define EG_TALLY_GROUPS_MAX (1u << 24)
+size_t eg_choice_tally_grouped_scratch_bytes(const eg_choice_params*, size_t n, uint32_t n_groups);
+int eg_choice_tally_grouped_device(eg_choice_params*, size_t n, const void* d_ballots, const void* d_status, const void* d_groups,
+                                   uint32_t n_groups, void* d_scratch, void* d_tallies, void* d_counts /* may be NULL */,
+                                   void* d_bad /* 2 x uint32 */, void* stream);
+int eg_choice_tally_grouped(eg_choice_params*, size_t n, const uint8_t* ballots, const uint32_t* status, const uint32_t* groups,
+                            uint32_t n_groups, uint8_t* tallies, uint32_t* counts /* may be NULL */);
+size_t eg_qv_tally_grouped_scratch_bytes(const eg_qv_params*, size_t n, uint32_t n_groups);
+int eg_qv_tally_grouped_device(eg_qv_params*, size_t n, const void* d_ballots, const void* d_status, const void* d_groups,
+                               uint32_t n_groups, void* d_scratch, void* d_tallies, void* d_counts /* may be NULL */,
+                               void* d_bad /* 2 x uint32 */, void* stream);
+int eg_qv_tally_grouped(eg_qv_params*, size_t n, const uint8_t* ballots, const uint32_t* status, const uint32_t* groups,
+                        uint32_t n_groups, uint8_t* tallies, uint32_t* counts /* may be NULL */);
+
 /* ---- batch tier on several GPUs of ONE process (SURVEY.md 8b `device_mask`; the reference's host is one single-threaded process,
  * examples/voting.rs:179-213) -----------------------------------------------------------------------------------------------------
  * per_device[d], d < n_dev: params objects of the SAME election (same key, options, kind), each created on its own context

@@ -18,6 +18,7 @@
 #include <optional>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "eg_hip.h"
@@ -116,6 +117,19 @@ inline std::vector<Ciphertext> unpack_totals(const Bytes& t) {
   return out;
 }
 
+// Per-group tally of a verified batch (eg_*_tally_grouped): totals[g] = what the verify call's totals would be for the ballots of group
+// g alone; accepted[g] = how many of them were accepted.
+struct GroupedTally {
+  std::vector<std::vector<Ciphertext>> totals;
+  std::vector<uint32_t> accepted;
+};
+inline GroupedTally unpack_grouped(const Bytes& t, std::vector<uint32_t> counts, size_t options) {
+  GroupedTally g;
+  g.accepted = std::move(counts);
+  for (size_t k = 0; k < g.accepted.size(); ++k) g.totals.push_back(unpack_totals(Bytes(t.begin() + 64 * options * k, t.begin() + 64 * options * (k + 1))));
+  return g;
+}
+
 // ChoiceParams<G, S> (choice.rs:132-196); S is SingleChoice (sum proof) or MultiChoice
 class ChoiceParams {
  public:
@@ -157,6 +171,24 @@ class ChoiceParams {
   // asynchronous device-pointer form of verify_small: verdicts into d_status, accepted ballots into the running tally
   void verify_small_device(size_t n, const void* d_ballots, void* d_status, void* stream = nullptr) const {
     check(eg_verify_choice_small_device(p_, n, d_ballots, d_status, stream));
+  }
+  // per-group tally of a verified batch: `status` = the words a verify entry wrote for `packed` (0 = accepted), groups[b] = group of ballot b
+  // (EG_GROUP_NONE: in no group).  Stateless; throws EG_ERR_BAD_ARG for an accepted ballot with an id >= n_groups or an undecodable point.
+  GroupedTally tally_grouped(const Bytes& packed, const std::vector<uint32_t>& status, const std::vector<uint32_t>& groups, uint32_t n_groups) const {
+    const size_t n = packed.size() / ballot_size();
+    if (n * ballot_size() != packed.size() || status.size() != n || groups.size() != n)
+      throw Error(EG_ERR_BAD_ARG, "packed, status and groups do not describe the same number of ballots");
+    if (n_groups == 0 || n_groups > EG_TALLY_GROUPS_MAX) throw Error(EG_ERR_BAD_ARG, "n_groups out of range");
+    Bytes tallies((size_t)n_groups * 64 * n_);
+    std::vector<uint32_t> counts(n_groups);
+    check(eg_choice_tally_grouped(p_, n, packed.data(), status.data(), groups.data(), n_groups, tallies.data(), counts.data()));
+    return unpack_grouped(tallies, std::move(counts), n_);
+  }
+  // asynchronous device-pointer form: d_scratch of tally_grouped_scratch_bytes(n, n_groups) bytes, d_bad two uint32 the library writes
+  size_t tally_grouped_scratch_bytes(size_t n, uint32_t n_groups) const { return eg_choice_tally_grouped_scratch_bytes(p_, n, n_groups); }
+  void tally_grouped_device(size_t n, const void* d_ballots, const void* d_status, const void* d_groups, uint32_t n_groups, void* d_scratch,
+                            void* d_tallies, void* d_counts, void* d_bad, void* stream = nullptr) const {
+    check(eg_choice_tally_grouped_device(p_, n, d_ballots, d_status, d_groups, n_groups, d_scratch, d_tallies, d_counts, d_bad, stream));
   }
   // EncryptedChoice::new for synthetic voters base_seed + first + i (choice.rs:313-349), packed
   Bytes encrypt_batch(uint64_t base_seed, size_t first, size_t n, int n_selected = 0) const {
@@ -225,6 +257,24 @@ class QuadraticVotingParams {
   }
   void verify_small_device(size_t n, const void* d_ballots, void* d_status, void* stream = nullptr) const {
     check(eg_verify_qv_small_device(p_, n, d_ballots, d_status, stream));
+  }
+  // per-group tally of a verified batch: `status` = the words a verify entry wrote for `packed` (0 = accepted), groups[b] = group of ballot b
+  // (EG_GROUP_NONE: in no group).  Stateless; throws EG_ERR_BAD_ARG for an accepted ballot with an id >= n_groups or an undecodable point.
+  GroupedTally tally_grouped(const Bytes& packed, const std::vector<uint32_t>& status, const std::vector<uint32_t>& groups, uint32_t n_groups) const {
+    const size_t n = packed.size() / ballot_size();
+    if (n * ballot_size() != packed.size() || status.size() != n || groups.size() != n)
+      throw Error(EG_ERR_BAD_ARG, "packed, status and groups do not describe the same number of ballots");
+    if (n_groups == 0 || n_groups > EG_TALLY_GROUPS_MAX) throw Error(EG_ERR_BAD_ARG, "n_groups out of range");
+    Bytes tallies((size_t)n_groups * 64 * n_);
+    std::vector<uint32_t> counts(n_groups);
+    check(eg_qv_tally_grouped(p_, n, packed.data(), status.data(), groups.data(), n_groups, tallies.data(), counts.data()));
+    return unpack_grouped(tallies, std::move(counts), n_);
+  }
+  // asynchronous device-pointer form: d_scratch of tally_grouped_scratch_bytes(n, n_groups) bytes, d_bad two uint32 the library writes
+  size_t tally_grouped_scratch_bytes(size_t n, uint32_t n_groups) const { return eg_qv_tally_grouped_scratch_bytes(p_, n, n_groups); }
+  void tally_grouped_device(size_t n, const void* d_ballots, const void* d_status, const void* d_groups, uint32_t n_groups, void* d_scratch,
+                            void* d_tallies, void* d_counts, void* d_bad, void* stream = nullptr) const {
+    check(eg_qv_tally_grouped_device(p_, n, d_ballots, d_status, d_groups, n_groups, d_scratch, d_tallies, d_counts, d_bad, stream));
   }
   // QuadraticVotingBallot::new(&params, votes, rng) for voters base_seed + first + i (quadratic_voting.rs:234-284); votes:
   // options_count() numbers per voter with sum(v^2) <= credits.  VARIABLE TIME in the votes (see eg_hip.h): test / synthetic data only.
