@@ -9,6 +9,7 @@
 #include "../../elastic_elgamal_amd/csrc/sc25519.cuh"
 #include "../../elastic_elgamal_amd/csrc/merlin.cuh"
 #include "../devcheck/limb_ops.cuh"
+#include "../merlindev/transcript_script.cuh"
 
 using namespace eg;
 
@@ -262,6 +263,20 @@ extern "C" int hc_merlin(const char* label, const char* l1, const uint8_t* m1, i
   u32 o[16]; merlin_challenge64(c, l3, (int)strlen(l3), o);
   bytes_from_words(out, o, 16);
   return (int)t.pos;
+}
+
+// n cases of one transcript script (tests/merlindev/transcript_script.cuh, tests/transcript_scripts.py): blob = the script, msgs = n
+// message areas of msg_bytes bytes, out = n x out_words words (zeroed here).  Returns 0, or -1 for a script that does not fit its buffers.
+extern "C" int hc_transcript_script(const uint32_t* blob, size_t blob_bytes, int n, const uint32_t* msgs, size_t msg_bytes, uint32_t* out,
+                                    size_t out_words) {
+  const long need = ts_out_words(blob, blob_bytes, msg_bytes);
+  if (need < 0 || (size_t)need != out_words || n < 0 || (n && (!msgs || !out))) return -1;
+  memset(out, 0, sizeof(uint32_t) * out_words * (size_t)n);
+  for (int i = 0; i < n; ++i) {
+    Transcript<ArrState> a, b;
+    ts_run(a, b, blob, msgs + (msg_bytes / 4) * (size_t)i, out + out_words * (size_t)i);
+  }
+  return 0;
 }
 
 // field operation counts of the hot-path building blocks: out[2*i], out[2*i+1] = (fe_mul, fe_sq) calls of

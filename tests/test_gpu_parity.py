@@ -520,6 +520,48 @@ def test_merlin_known_answers_on_the_gpu(eg, ctx, oracle):
                 assert g == t.challenge(b"c", out_len), (n, out_len)
 
 
+def test_merlin_entry_at_its_own_edges(eg, ctx, oracle):
+    """eg_merlin_challenge_batch where its own arguments meet the 166-byte STROBE block: protocol, message and challenge labels of 0, 1,
+    165, 166, 167 and 255 bytes in every combination (bytes 1..255, one >= 0x80 at least), message lengths 0, 163..167 and 331..333
+    with every challenge length of 1, 165, 166, 167, 332 and 1024 bytes, batches of 1, 63, 64, 65 and 257 distinct messages - all
+    against the oracle's transcript - and what the entry refuses."""
+    import ctypes as C
+
+    import transcript_scripts as ts
+
+    labels, msg_lens, out_lens, ns = (0, 1, 165, 166, 167, 255), (0, 163, 164, 165, 166, 167, 331, 332, 333), (1, 165, 166, 167, 332, 1024), \
+        (1, 63, 64, 65, 257)
+    cases = [(p, m, c, msg_lens[(k // 6) % 9], out_lens[k % 6]) for k, (p, m, c) in
+             enumerate((p, m, c) for p in labels for m in labels for c in labels)]
+    cases += [(labels[k % 6], labels[(k // 6) % 6], labels[(k // 2) % 6], ml, ol) for k, (ml, ol) in
+              enumerate((ml, ol) for ml in msg_lens for ol in out_lens)]
+    assert {(p, m, c) for p, m, c, _, _ in cases} >= {(p, m, c) for p in labels for m in labels for c in labels}
+    assert {(ml, ol) for _, _, _, ml, ol in cases} == {(ml, ol) for ml in msg_lens for ol in out_lens}
+    rnd = random.Random(71)
+    for k, (p, m, c, ml, ol) in enumerate(cases):
+        n = ns[k % 5]
+        proto, msg_label, chal_label = ts.label_bytes(p, 50), ts.label_bytes(m, 51), ts.label_bytes(c, 52)
+        msgs = [i.to_bytes(2, "little") + rnd.getrandbits(8 * ml).to_bytes(ml, "little")[2:] if ml else b"" for i in range(n)]
+        got = ctx.merlin_challenges(proto, msg_label, msgs, chal_label, ol)
+        assert len(got) == n
+        for i, (msg, g) in enumerate(zip(msgs, got)):
+            t = oracle.Merlin(proto); t.append(msg_label, msg)
+            assert g == t.challenge(chal_label, ol), (p, m, c, ml, ol, n, i)
+    long_label = ts.label_bytes(256, 53)
+    for args in ((long_label, b"m", b"c", 64), (b"p", long_label, b"c", 64), (b"p", b"m", long_label, 64), (b"p", b"m", b"c", 0),
+                 (b"p", b"m", b"c", 1025)):
+        with pytest.raises(eg.EgError):
+            ctx.merlin_challenges(args[0], args[1], [b"msg"], args[2], args[3])
+    lib, out = eg._load(), C.create_string_buffer(1025)
+    BAD_ARG = -3                                      # include/eg_hip.h: EG_ERR_BAD_ARG
+    assert lib.eg_merlin_challenge_batch(ctx._h, 1, long_label, 256, b"m", 1, b"msg", 3, b"c", 1, out, 64) == BAD_ARG
+    assert lib.eg_merlin_challenge_batch(ctx._h, 1, b"p", 1, long_label, 256, b"msg", 3, b"c", 1, out, 64) == BAD_ARG
+    assert lib.eg_merlin_challenge_batch(ctx._h, 1, b"p", 1, b"m", 1, b"msg", 3, long_label, 256, out, 64) == BAD_ARG
+    assert lib.eg_merlin_challenge_batch(ctx._h, 1, b"p", 1, b"m", 1, b"msg", 3, b"c", 1, out, 0) == BAD_ARG
+    assert lib.eg_merlin_challenge_batch(ctx._h, 1, b"p", 1, b"m", 1, b"msg", 3, b"c", 1, out, 1025) == BAD_ARG
+    assert lib.eg_merlin_challenge_batch(ctx._h, 1, b"p", 1, b"m", 1, b"msg", 3, b"c", 1, out, 1024) == 0
+
+
 # ------------------------------------------------------------------ PublicKey::verify_zero / verify_bool / verify_range
 def test_golden_single_ciphertext_proofs(eg, ctx, golden, pk, oracle):
     z = eg.PublicKeyVerifier(ctx, pk, eg.PublicKeyVerifier.ZERO)

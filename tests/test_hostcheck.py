@@ -17,7 +17,7 @@ P = 2**255 - 19
 @pytest.fixture(scope="module")
 def hc():
     lib = HERE / "libhostcheck.so"
-    srcs = [HERE / "hostcheck.cpp", HERE.parent / "devcheck" / "limb_ops.cuh"] + list((HERE.parent.parent / "elastic_elgamal_amd" / "csrc").glob("*.cuh"))
+    srcs = [HERE / "hostcheck.cpp", HERE.parent / "devcheck" / "limb_ops.cuh", HERE.parent / "merlindev" / "transcript_script.cuh"] + list((HERE.parent.parent / "elastic_elgamal_amd" / "csrc").glob("*.cuh"))
     if not lib.exists() or any(s.stat().st_mtime > lib.stat().st_mtime for s in srcs):
         subprocess.check_call(
             ["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-DEG_BOUNDCHECK", "-fsanitize=undefined",
