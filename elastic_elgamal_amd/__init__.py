@@ -186,6 +186,12 @@ def _load() -> C.CDLL:
         "eg_qv_tally_grouped_scratch_bytes": (sz, [vp, sz, C.c_uint32]),
         "eg_qv_tally_grouped_device": (C.c_int, [vp, sz, vp, vp, vp, C.c_uint32, vp, vp, vp, vp, vp]),
         "eg_qv_tally_grouped": (C.c_int, [vp, sz, vp, vp, vp, C.c_uint32, vp, vp]),
+        "eg_choice_tally_weighted_scratch_bytes": (sz, [vp, sz, C.c_uint32]),
+        "eg_choice_tally_weighted_device": (C.c_int, [vp, sz, vp, vp, vp, C.c_int, vp, C.c_uint32, vp, vp, vp, vp, vp, vp]),
+        "eg_choice_tally_weighted": (C.c_int, [vp, sz, vp, vp, vp, C.c_int, vp, C.c_uint32, vp, vp, vp]),
+        "eg_qv_tally_weighted_scratch_bytes": (sz, [vp, sz, C.c_uint32]),
+        "eg_qv_tally_weighted_device": (C.c_int, [vp, sz, vp, vp, vp, C.c_int, vp, C.c_uint32, vp, vp, vp, vp, vp, vp]),
+        "eg_qv_tally_weighted": (C.c_int, [vp, sz, vp, vp, vp, C.c_int, vp, C.c_uint32, vp, vp, vp]),
         "eg_proof_params_create": (C.c_int, [vp, cp, C.c_int, C.c_uint64, C.POINTER(vp)]),
         "eg_share_params_create": (C.c_int, [vp, cp, C.c_uint64, C.c_uint64, C.c_uint64, cp, C.POINTER(vp)]),
         "eg_proof_params_destroy": (None, [vp]),
@@ -876,6 +882,49 @@ class _BatchParams:
         the caller must read them and discard the tallies if either is non-zero."""
         _check(self._fn("tally_grouped_device")(self._h, n, d_ballots or None, d_status or None, d_groups or None, n_groups,
                                                  d_scratch or None, d_tallies or None, d_counts or None, d_bad or None, stream or None))
+
+    def tally_weighted_scratch_bytes(self, n: int, n_groups: int = 1) -> int:
+        """Device scratch that tally_weighted_device needs for n ballots in n_groups groups (0 for arguments it refuses)."""
+        return int(self._fn("tally_weighted_scratch_bytes")(self._h, n, n_groups))
+
+    def tally_weighted(self, ballots: bytes, status, weights, groups=None, n_groups: int = 1, weight_bits: int = 64):
+        """Weighted per-group tally of the accepted ballots of a verified batch (eg_*_tally_weighted): ballot b adds weights[b] times
+        its ciphertexts to the tally of groups[b] (`groups` None: one group).  weights[b] < 2**weight_bits <= 2**64; weight_bits fixes
+        the cost per point, so pass the smallest bound that holds.  Returns (tallies, weight_sums, counts): tallies as tally_grouped,
+        weight_sums[g] = the exact sum of the counted weights of group g (a Python int, the bound for DlogSolver.solve), counts[g] =
+        its accepted ballots.  Stateless.  A stray group id, a tally point that does not decode or a weight of 2**weight_bits or more
+        on an accepted ballot fails the call (EG_ERR_BAD_ARG)."""
+        n = len(ballots) // self.ballot_size
+        if n * self.ballot_size != len(ballots):
+            raise ValueError("ballots is not a whole number of packed ballots")
+        status, weights = list(status), list(weights)
+        if len(status) != n or len(weights) != n or (groups is not None and len(groups) != n):
+            raise ValueError("status, weights and groups need one word per ballot")
+        if any(not 0 <= int(w) < 1 << 64 for w in weights):
+            raise ValueError("a weight is outside 0 .. 2^64 - 1")
+        st = (C.c_uint32 * max(n, 1))(*status)
+        wt = (C.c_uint64 * max(n, 1))(*weights)
+        gr = None if groups is None else (C.c_uint32 * max(n, 1))(*groups)
+        buf = (C.c_char * max(len(ballots), 1)).from_buffer_copy(ballots or b"\0")
+        ng = max(int(n_groups), 0)
+        if not 0 < ng <= TALLY_GROUPS_MAX:                     # refused by the library: no output buffers of that size are made
+            _check(self._fn("tally_weighted")(self._h, n, buf, st, wt, weight_bits, gr, ng & 0xFFFFFFFF, None, None, None))
+            raise EgError("eg_*_tally_weighted accepted a group count it must refuse")
+        tallies = C.create_string_buffer(ng * 64 * self.n_options)
+        sums = (C.c_uint64 * (2 * ng))()
+        counts = (C.c_uint32 * ng)()
+        _check(self._fn("tally_weighted")(self._h, n, buf, st, wt, weight_bits, gr, ng, tallies, sums, counts))
+        return tallies.raw, [sums[2 * g] | (sums[2 * g + 1] << 64) for g in range(ng)], list(counts)
+
+    def tally_weighted_device(self, n: int, d_ballots: int, d_status: int, d_weights: int, weight_bits: int, d_groups: int, n_groups: int,
+                              d_scratch: int, d_tallies: int, d_bad: int, d_weight_sums: int = 0, d_counts: int = 0, stream: int = 0):
+        """Asynchronous device-pointer variant (eg_*_tally_weighted_device): no allocation, no host synchronisation.  d_weights: n
+        uint64; d_groups may be 0 (one group); d_scratch: tally_weighted_scratch_bytes(n, n_groups) bytes; d_weight_sums: n_groups x
+        (low, high) uint64; d_bad: three uint32 the library writes (ids out of range, undecodable points, weights out of range) - the
+        caller must read them and discard the results if any is non-zero."""
+        _check(self._fn("tally_weighted_device")(self._h, n, d_ballots or None, d_status or None, d_weights or None, weight_bits,
+                                                  d_groups or None, n_groups, d_scratch or None, d_tallies or None, d_weight_sums or None,
+                                                  d_counts or None, d_bad or None, stream or None))
 
 
 class ChoiceParams(_BatchParams):

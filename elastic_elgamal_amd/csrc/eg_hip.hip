@@ -1951,6 +1951,18 @@ static int grouped_check(const Engine* e, size_t n, uint32_t n_groups) {
   if (!e) return fail(EG_ERR_BAD_ARG, "grouped tally: null params");
   return EG_OK;
 }
+// the scan of the group counts in the caller's scratch: list offsets, pieces and first piece per group for every level (three launches)
+static GtScan grouped_scan(const eggt::Layout& L, char* base, uint32_t n_groups, hipStream_t s) {
+  auto at = [&](size_t o) { return reinterpret_cast<u32*>(base + o); };
+  GtScan S;
+  S.offsets = at(L.offsets); S.totals = at(L.totals); S.tile_sums = at(L.tiles);
+  for (int l = 0; l < eggt::MAX_LEVELS; ++l) { S.pieces[l] = at(L.pieces[l]); S.piece0[l] = at(L.piece0[l]); }
+  const u32* counts = at(L.counts);
+  hipLaunchKernelGGL(k_gt_scan_tiles, dim3(L.n_tiles), dim3(NT), 0, s, counts, n_groups, L.n_levels, eggt::S1, eggt::S2, S);
+  hipLaunchKernelGGL(k_gt_scan_tops, dim3(1), dim3(64 * GT_SEQ), 0, s, L.n_tiles, S);
+  hipLaunchKernelGGL(k_gt_scan_apply, dim3(L.n_tiles), dim3(NT), 0, s, counts, n_groups, L.n_levels, eggt::S1, eggt::S2, S);
+  return S;
+}
 static int grouped_launch(Engine* e, size_t n, const void* d_ballots, const void* d_status, const void* d_groups, uint32_t n_groups,
                           void* d_scratch, void* d_tallies, void* d_counts, void* d_bad, hipStream_t s) {
   TRY_(grouped_check(e, n, n_groups));
@@ -1975,12 +1987,7 @@ static int grouped_launch(Engine* e, size_t n, const void* d_ballots, const void
   if (bad) HIPCHK(hipMemsetAsync(bad, 0, 2 * sizeof(u32), s));
   HIPCHK(hipMemsetAsync(counts, 0, L.offsets - L.counts, s));          // counts and cursors
   if (n) hipLaunchKernelGGL(k_gt_count, dim3(blocks_of(n)), dim3(NT), 0, s, (u32)n, status, groups, n_groups, counts, bad);
-  GtScan S;
-  S.offsets = offsets; S.totals = totals; S.tile_sums = at(L.tiles);
-  for (int l = 0; l < eggt::MAX_LEVELS; ++l) { S.pieces[l] = at(L.pieces[l]); S.piece0[l] = at(L.piece0[l]); }
-  hipLaunchKernelGGL(k_gt_scan_tiles, dim3(L.n_tiles), dim3(NT), 0, s, (const u32*)counts, n_groups, L.n_levels, eggt::S1, eggt::S2, S);
-  hipLaunchKernelGGL(k_gt_scan_tops, dim3(1), dim3(64 * GT_SEQ), 0, s, L.n_tiles, S);
-  hipLaunchKernelGGL(k_gt_scan_apply, dim3(L.n_tiles), dim3(NT), 0, s, (const u32*)counts, n_groups, L.n_levels, eggt::S1, eggt::S2, S);
+  const GtScan S = grouped_scan(L, static_cast<char*>(d_scratch), n_groups, s);
   const u32 *cnt = counts, *off = offsets;
   if (n) {
     hipLaunchKernelGGL(k_gt_fill, dim3(blocks_of(n)), dim3(NT), 0, s, (u32)n, status, groups, n_groups, (const u32*)offsets, cursors, idx);
@@ -2059,6 +2066,149 @@ int eg_choice_tally_grouped(eg_choice_params* p, size_t n, const uint8_t* ballot
 int eg_qv_tally_grouped(eg_qv_params* p, size_t n, const uint8_t* ballots, const uint32_t* status, const uint32_t* groups, uint32_t n_groups,
                         uint8_t* tallies, uint32_t* counts) {
   return grouped_host(p ? p->eng : nullptr, n, ballots, status, groups, n_groups, tallies, counts);
+}
+// ---- weighted per-group tally: the same pass with [weight] x point at level 0 and the sums of weights beside the points -----------------
+// Stateless like the grouped pass: the plan's immutable data only.
+static size_t weighted_scratch_bytes(const Engine* e, size_t n, uint32_t n_groups) {
+  if (!e || eggt::refuse(n, n_groups)) return 0;
+  return eggt::layout_weighted(n, n_groups, (uint32_t)e->plan.tally_slots.size()).total;
+}
+static int weighted_check(const Engine* e, size_t n, uint32_t n_groups, int weight_bits, bool have_weights, bool have_groups) {
+  const char* why = eggt::refuse(n, n_groups);
+  if (!why) why = eggt::refuse_weight_bits(weight_bits);
+  if (!why && n && !have_weights) why = "null weights";
+  if (!why && !have_groups && n_groups != 1) why = "null groups stand for one group: n_groups must be 1";
+  if (why) return fail(EG_ERR_BAD_ARG, std::string("weighted tally: ") + why);
+  if (!e) return fail(EG_ERR_BAD_ARG, "weighted tally: null params");
+  return EG_OK;
+}
+static int weighted_launch(Engine* e, size_t n, const void* d_ballots, const void* d_status, const void* d_weights, int weight_bits,
+                           const void* d_groups, uint32_t n_groups, void* d_scratch, void* d_tallies, void* d_weight_sums, void* d_counts,
+                           void* d_bad, hipStream_t s) {
+  TRY_(weighted_check(e, n, n_groups, weight_bits, d_weights != nullptr, d_groups != nullptr));
+  if (n && (!d_ballots || !d_status || !d_tallies || !d_bad)) return fail(EG_ERR_BAD_ARG, "weighted tally: null device pointer");
+  if (!d_tallies) return EG_OK;                                          // n == 0 and nowhere to write the zero tallies to
+  const u32 T = (u32)e->plan.tally_slots.size();
+  const eggt::WeightedLayout W = eggt::layout_weighted(n, n_groups, T);
+  const eggt::Layout& L = W.base;
+  if (W.total && !d_scratch) return fail(EG_ERR_BAD_ARG, "weighted tally: null scratch (eg_*_tally_weighted_scratch_bytes says how much)");
+  if (((uintptr_t)d_ballots | (uintptr_t)d_scratch) & 15u) return fail(EG_ERR_BAD_ARG, "weighted tally: ballots and scratch must be 16-byte aligned");
+  if (((uintptr_t)d_weights | (uintptr_t)d_weight_sums) & 7u) return fail(EG_ERR_BAD_ARG, "weighted tally: weights and weight sums must be 8-byte aligned");
+  if (((uintptr_t)d_status | (uintptr_t)d_groups | (uintptr_t)d_tallies | (uintptr_t)d_counts | (uintptr_t)d_bad) & 3u)
+    return fail(EG_ERR_BAD_ARG, "weighted tally: misaligned device pointer");
+  if (L.n_levels > eggt::MAX_LEVELS) return fail(EG_ERR_BAD_ARG, "weighted tally: too many ballots");
+  HIPCHK(hipSetDevice(e->ctx->device));
+  char* base = static_cast<char*>(d_scratch);
+  auto at = [&](size_t o) { return reinterpret_cast<u32*>(base + o); };
+  u32 *counts = at(L.counts), *cursors = at(L.cursors), *offsets = at(L.offsets), *totals = at(L.totals), *idx = at(L.idx);
+  uint4* psum[2] = {reinterpret_cast<uint4*>(base + L.psum[0]), reinterpret_cast<uint4*>(base + L.psum[1])};
+  u64* wsum[2] = {reinterpret_cast<u64*>(base + W.wsum[0]), reinterpret_cast<u64*>(base + W.wsum[1])};
+  const u32* status = static_cast<const u32*>(d_status);
+  const u32* groups = static_cast<const u32*>(d_groups);
+  const GtWeightsDev weights{static_cast<const u64*>(d_weights), (u32)n};
+  u32* bad = static_cast<u32*>(d_bad);
+  const int cap = e->ctx->cus * 64;
+  if (bad) HIPCHK(hipMemsetAsync(bad, 0, 3 * sizeof(u32), s));
+  HIPCHK(hipMemsetAsync(counts, 0, L.offsets - L.counts, s));          // counts and cursors
+  if (n) hipLaunchKernelGGL(k_gtw_count, dim3(blocks_of(n)), dim3(NT), 0, s, (u32)n, status, groups, n_groups, weights, weight_bits, counts, bad);
+  const GtScan S = grouped_scan(L, static_cast<char*>(d_scratch), n_groups, s);
+  const u32 *cnt = counts, *off = offsets;
+  if (n) {
+    hipLaunchKernelGGL(k_gtw_fill, dim3(blocks_of(n)), dim3(NT), 0, s, (u32)n, status, groups, n_groups, weights, weight_bits,
+                       (const u32*)offsets, cursors, idx);
+    for (int l = 0; l < L.n_levels; ++l) {
+      const GtLevel lv{cnt, off, S.piece0[l]};
+      const size_t cap_pieces = L.psum_points[l & 1];
+      const int grid = grid_for(cap_pieces * T, cap);
+      if (l == 0) {
+        hipLaunchKernelGGL(k_gtw_sum_wire, dim3(grid), dim3(NT), 0, s, eggt::S1, T, lv, (const u32*)(totals + l), n_groups, (const u32*)idx,
+                           GtWireDev{static_cast<const u32*>(d_ballots), (u32)(e->plan.stride / 4), (u32)n}, (const u32*)e->d_tally_items,
+                           weights, weight_bits, psum[0], wsum[0], bad);
+      } else {
+        hipLaunchKernelGGL(k_gt_sum_points, dim3(grid), dim3(NT), 0, s, eggt::S2, T, lv, (const u32*)(totals + l), n_groups,
+                           (const uint4*)psum[(l - 1) & 1], psum[l & 1]);
+        if (d_weight_sums)
+          hipLaunchKernelGGL(k_gtw_weight_sums, dim3(grid_for(cap_pieces, cap)), dim3(NT), 0, s, eggt::S2, lv, (const u32*)(totals + l), n_groups,
+                             (const u64*)wsum[(l - 1) & 1], wsum[l & 1]);
+      }
+      cnt = S.pieces[l]; off = S.piece0[l];
+    }
+  }
+  const int last = L.n_levels - 1;
+  hipLaunchKernelGGL(k_gt_encode, dim3(grid_for((size_t)n_groups * T, cap)), dim3(NT), 0, s, n_groups, T, (const u32*)S.pieces[last],
+                     (const u32*)S.piece0[last], (const uint4*)psum[last & 1], (const u32*)counts, static_cast<u32*>(d_tallies),
+                     static_cast<u32*>(d_counts));
+  if (d_weight_sums)
+    hipLaunchKernelGGL(k_gtw_weight_sums_out, dim3(grid_for(n_groups, cap)), dim3(NT), 0, s, n_groups, (const u32*)S.pieces[last],
+                       (const u32*)S.piece0[last], (const u64*)wsum[last & 1], static_cast<u64*>(d_weight_sums));
+  HIPCHK(hipGetLastError());
+  return EG_OK;
+}
+// host buffers, staged as grouped_host stages them
+static int weighted_host(Engine* e, size_t n, const uint8_t* ballots, const uint32_t* status, const uint64_t* weights, int weight_bits,
+                         const uint32_t* groups, uint32_t n_groups, uint8_t* tallies, uint64_t* weight_sums, uint32_t* counts) {
+  TRY_(weighted_check(e, n, n_groups, weight_bits, weights != nullptr, groups != nullptr));
+  if (!tallies || (n && (!ballots || !status))) return fail(EG_ERR_BAD_ARG, "weighted tally: null pointer");
+  HIPCHK(hipSetDevice(e->ctx->device));
+  const size_t T = e->plan.tally_slots.size(), stride = e->plan.stride;
+  enum { BALLOTS, STATUS, WEIGHTS, GROUPS, SCRATCH, TALLIES, SUMS, COUNTS, N_BUF };
+  const size_t sizes[N_BUF] = {n * stride, n * 4, n * 8, groups ? n * 4 : 0, weighted_scratch_bytes(e, n, n_groups), (size_t)n_groups * T * 32,
+                               (size_t)n_groups * 16, (size_t)n_groups * 4 + 12};
+  void* d[N_BUF] = {};
+  hipStream_t s = nullptr;
+  ScopeExit release{[&]() {
+    for (void* p : d) if (p) (void)hipFree(p);
+    if (s) (void)hipStreamDestroy(s);
+  }};
+  for (int k = 0; k < N_BUF; ++k) {
+    const hipError_t he = hipMalloc(&d[k], std::max<size_t>(sizes[k], 16));
+    if (he == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(EG_ERR_NOMEM, "weighted tally: the staging buffers do not fit the device memory"); }
+    HIPCHK(he);
+  }
+  HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+  if (n) {
+    HIPCHK(hipMemcpyAsync(d[BALLOTS], ballots, sizes[BALLOTS], hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d[STATUS], status, sizes[STATUS], hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d[WEIGHTS], weights, sizes[WEIGHTS], hipMemcpyHostToDevice, s));
+    if (groups) HIPCHK(hipMemcpyAsync(d[GROUPS], groups, sizes[GROUPS], hipMemcpyHostToDevice, s));
+  }
+  u32* d_counts = static_cast<u32*>(d[COUNTS]);
+  u32* d_bad = d_counts + n_groups;
+  TRY_(weighted_launch(e, n, d[BALLOTS], d[STATUS], d[WEIGHTS], weight_bits, groups ? d[GROUPS] : nullptr, n_groups, d[SCRATCH], d[TALLIES],
+                       d[SUMS], d_counts, d_bad, s));
+  u32 bad[3] = {0, 0, 0};
+  HIPCHK(hipMemcpyAsync(tallies, d[TALLIES], sizes[TALLIES], hipMemcpyDeviceToHost, s));
+  if (weight_sums) HIPCHK(hipMemcpyAsync(weight_sums, d[SUMS], sizes[SUMS], hipMemcpyDeviceToHost, s));
+  if (counts) HIPCHK(hipMemcpyAsync(counts, d_counts, (size_t)n_groups * 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  if (bad[0] || bad[1] || bad[2])
+    return fail(EG_ERR_BAD_ARG, "weighted tally: " + std::to_string(bad[0]) + " accepted ballot(s) with a group id out of range, " +
+                                    std::to_string(bad[1]) + " tally point(s) of accepted ballots that do not decode, " + std::to_string(bad[2]) +
+                                    " weight(s) of 2^weight_bits or more: discard the tallies");
+  return EG_OK;
+}
+size_t eg_choice_tally_weighted_scratch_bytes(const eg_choice_params* p, size_t n, uint32_t n_groups) { return weighted_scratch_bytes(p ? p->eng : nullptr, n, n_groups); }
+size_t eg_qv_tally_weighted_scratch_bytes(const eg_qv_params* p, size_t n, uint32_t n_groups) { return weighted_scratch_bytes(p ? p->eng : nullptr, n, n_groups); }
+int eg_choice_tally_weighted_device(eg_choice_params* p, size_t n, const void* d_ballots, const void* d_status, const void* d_weights, int weight_bits,
+                                    const void* d_groups, uint32_t n_groups, void* d_scratch, void* d_tallies, void* d_weight_sums, void* d_counts,
+                                    void* d_bad, void* stream) {
+  return weighted_launch(p ? p->eng : nullptr, n, d_ballots, d_status, d_weights, weight_bits, d_groups, n_groups, d_scratch, d_tallies,
+                         d_weight_sums, d_counts, d_bad, (hipStream_t)stream);
+}
+int eg_qv_tally_weighted_device(eg_qv_params* p, size_t n, const void* d_ballots, const void* d_status, const void* d_weights, int weight_bits,
+                                const void* d_groups, uint32_t n_groups, void* d_scratch, void* d_tallies, void* d_weight_sums, void* d_counts,
+                                void* d_bad, void* stream) {
+  return weighted_launch(p ? p->eng : nullptr, n, d_ballots, d_status, d_weights, weight_bits, d_groups, n_groups, d_scratch, d_tallies,
+                         d_weight_sums, d_counts, d_bad, (hipStream_t)stream);
+}
+int eg_choice_tally_weighted(eg_choice_params* p, size_t n, const uint8_t* ballots, const uint32_t* status, const uint64_t* weights, int weight_bits,
+                             const uint32_t* groups, uint32_t n_groups, uint8_t* tallies, uint64_t* weight_sums, uint32_t* counts) {
+  return weighted_host(p ? p->eng : nullptr, n, ballots, status, weights, weight_bits, groups, n_groups, tallies, weight_sums, counts);
+}
+int eg_qv_tally_weighted(eg_qv_params* p, size_t n, const uint8_t* ballots, const uint32_t* status, const uint64_t* weights, int weight_bits,
+                         const uint32_t* groups, uint32_t n_groups, uint8_t* tallies, uint64_t* weight_sums, uint32_t* counts) {
+  return weighted_host(p ? p->eng : nullptr, n, ballots, status, weights, weight_bits, groups, n_groups, tallies, weight_sums, counts);
 }
 // builds the wide comb tables now (synchronously, ~12 GB each for G and K) instead of inside the first large verify call
 static int prepare_wide(Engine* e) {

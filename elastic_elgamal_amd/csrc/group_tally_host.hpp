@@ -1,5 +1,6 @@
 // group_tally_host.hpp -- arithmetic of the per-group tally (eg_*_tally_grouped*, eg_hip.hip; kernels: group_tally_kernels.cuh): pure host
-// code, no HIP.  tests/hostcheck/grouptallycheck.cpp compiles it under ASan + UBSan together with the lane functions of the kernels.
+// code, no HIP.  tests/hostcheck/grouptallycheck.cpp and weightedtallycheck.cpp compile it under ASan + UBSan together with the lane
+// functions of the kernels.
 //
 // The pass is a keyed sum of points: ballot b, if accepted, adds its 2 n_options ciphertext points to the tally of group groups[b].
 //   level 0      a group's list of accepted ballots is cut into PIECES of <= S1 ballots; one lane sums one tally slot of one piece
@@ -121,6 +122,33 @@ inline const char* refuse(size_t n, uint32_t n_groups) {
   if (n_groups > GROUPS_MAX) return "n_groups is above EG_TALLY_GROUPS_MAX";
   if ((uint64_t)n >= N_LIMIT) return "n is 2^31 or more";
   return nullptr;
+}
+
+// ---- the weighted pass (eg_*_tally_weighted*): ballot b adds [w_b] x its ciphertext points, w_b < 2^weight_bits ---------------------------
+// The same lists, pieces and levels; beside every partial sum of slot 0 travels the piece's sum of weights, a 128-bit number in two
+// 64-bit words (low, high): n < 2^31 weights below 2^64 stay below 2^95.
+constexpr size_t WSUM_BYTES = 16;
+
+// the grouped layout, and behind it one weight sum per piece for the same two alternating levels
+struct WeightedLayout {
+  Layout base;
+  size_t wsum[2], total;
+};
+inline WeightedLayout layout_weighted(size_t n, uint32_t n_groups, uint32_t n_slots, uint32_t s1 = S1, uint32_t s2 = S2) {
+  WeightedLayout W;
+  W.base = layout(n, n_groups, n_slots, s1, s2);
+  size_t off = W.base.total;
+  for (int k = 0; k < 2; ++k) { W.wsum[k] = off; off += (W.base.psum_points[k] * WSUM_BYTES + 255) / 256 * 256; }
+  W.total = off;
+  return W;
+}
+
+// does weight w fit weight_bits (1..64) bits
+EGGT_HD bool weight_fits(uint64_t w, int weight_bits) { return weight_bits >= 64 || (w >> weight_bits) == 0u; }
+
+// argument rules of eg_*_tally_weighted* beyond refuse()
+inline const char* refuse_weight_bits(int weight_bits) {
+  return weight_bits < 1 || weight_bits > 64 ? "weight_bits is outside 1..64" : nullptr;
 }
 
 }  // namespace eggt

@@ -21,6 +21,9 @@
 //                    the counts go out with slot 0
 // The lane bodies of the last three and gt_bucket_of are plain functions over their memory, so that the host check build
 // (tests/hostcheck/grouptallycheck.cpp, -DEG_BOUNDCHECK) runs the same code with other piece sizes on arrays.
+// The weighted pass (eg_*_tally_weighted*) is the same pass with [weights[b]] x point at level 0 (ge_mul_u64, gt_lane_wire_weighted), a weight
+// check in count and fill, and the exact sums of weights carried through the levels beside the points; it has kernels of its own for
+// those steps (k_gtw_*) and shares the scan, k_gt_sum_points and k_gt_encode (tests/hostcheck/weightedtallycheck.cpp runs its lane bodies).
 #pragma once
 #include "ge25519.cuh"
 #include "group_tally_host.hpp"
@@ -84,6 +87,89 @@ EG_HD void gt_lane_encode(u32 w[8], u32 g, u32 t, u32 n_slots, const u32* pieces
   ge p;
   in.load(p, (size_t)piece0[g] * n_slots + t);
   ristretto_encode(w, p);
+}
+
+// ---- the weighted pass (eg_*_tally_weighted*): tallies[g] = sum of [w_b] x the ciphertexts of g's accepted ballots, w_b < 2^bits ---------
+// r = [w mod 2^bits] p, 1 <= bits <= 64: a left-to-right binary ladder of exactly `bits` steps, the same instruction stream whatever w
+// is (lanes of a wavefront hold different weights): double, then add p or - by select - the identity.  ~16 field operations a bit; no
+// table (a radix-16 table is 1.1 KiB a lane, and the pass owns no workspace).  Bits of w at and above `bits` are NOT looked at: the
+// range check of the count / fill kernels is what keeps a longer weight out.
+EG_HD void ge_mul_u64(ge& r, const ge& p, u64 w, int bits) {
+  ge_cached pc, ident;
+  ge_to_cached(pc, p);
+  ge_cached_identity(ident);
+  ge_p2 q;
+  fe_0(q.X); fe_1(q.Y); fe_1(q.Z);
+#pragma unroll 1
+  for (int i = bits - 1; i >= 0; --i) {
+    const bool skip = ((w >> i) & 1u) == 0u;
+    ge_p1p1 t;
+    ge acc;
+    ge_dbl(t, q.X, q.Y, q.Z);
+    ge_dbl_to_p3(acc, t);
+    ge_cached c = pc;
+    fe_cmov(c.YpX, ident.YpX, skip); fe_cmov(c.YmX, ident.YmX, skip);
+    fe_cmov(c.Z2, ident.Z2, skip); fe_cmov(c.T2d, ident.T2d, skip);
+    ge_add(t, acc, c);
+    if (i > 0) ge_add_to_p2(q, t);      // next comes a doubling: T is not needed
+    else ge_add_to_p3(r, t);
+  }
+}
+
+// what the count and fill kernels decide about ballot b: 0 = not counted (rejected, or in no group), 1 = counted in group g, 2 = accepted
+// with a stray id (bad[0]), 3 = accepted, id in range, weight of more than `bits` bits (bad[2]).  Ids and weights of rejected ballots are
+// never read, weights of ballots in no group neither; groups == nullptr: every ballot in group 0.
+template <class WeightIO>
+EG_HD u32 gt_weighted_class(u32& g, u32 b, const u32* status, const u32* groups, u32 n_groups, const WeightIO& weights, int bits) {
+  g = eggt::GROUP_NONE;
+  if (status[b] != 0u) return 0u;
+  g = groups ? groups[b] : 0u;
+  if (g == eggt::GROUP_NONE) return 0u;
+  if (g >= n_groups) return 2u;
+  return eggt::weight_fits(weights.load(b), bits) ? 1u : 3u;
+}
+
+// level 0, slot t of piece u: the sum of [weight] x wire item `item` over the piece's ballots -> out[u n_slots + t]; the lane of slot 0
+// also leaves the piece's sum of weights in sums[u]
+template <class WireIO, class WeightIO, class PointIO, class SumIO, class Bad>
+EG_HD void gt_lane_wire_weighted(u32 u, u32 t, u32 n_slots, u32 s1, const GtLevel& L, u32 n_groups, const u32* idx, const WireIO& wire, u32 item,
+                                 const WeightIO& weights, int bits, PointIO& out, SumIO& sums, Bad& bad) {
+  u32 beg, end;
+  gt_piece_range(beg, end, L, n_groups, u, s1);
+  ge acc; ge_identity(acc);
+  u64 lo = 0, hi = 0;
+  for (u32 i = beg; i < end; ++i) {
+    const u32 b = idx[i];
+    u32 w[8];
+    wire.load(w, b, item);
+    const u64 k = weights.load(b);
+    ge p, m, sum;
+    if (!ristretto_decode(p, w)) bad.undecodable();      // p is then the identity
+    ge_mul_u64(m, p, k, bits);
+    ge_add_full(sum, acc, m); acc = sum;
+    lo += k; hi += lo < k ? 1u : 0u;
+  }
+  out.store((size_t)u * n_slots + t, acc);
+  if (t == 0u) sums.store(u, lo, hi);
+}
+// level l >= 1, piece u: the sum of up to s2 weight sums of the level before -> out[u]
+template <class SumIn, class SumOut>
+EG_HD void gt_lane_weight_sums(u32 u, u32 s2, const GtLevel& L, u32 n_groups, const SumIn& in, SumOut& out) {
+  u32 beg, end;
+  gt_piece_range(beg, end, L, n_groups, u, s2);
+  u64 lo = 0, hi = 0;
+  for (u32 i = beg; i < end; ++i) {
+    u64 a, c;
+    in.load(a, c, i);
+    lo += a; hi += c + (lo < a ? 1u : 0u);
+  }
+  out.store(u, lo, hi);
+}
+// group g after the last level (pieces[g] is 0 or 1): its sum of weights
+template <class SumIn>
+EG_HD void gt_lane_weight_sum_out(u64& lo, u64& hi, u32 g, const u32* pieces, const u32* piece0, const SumIn& in) {
+  lo = 0; hi = 0;
+  if (pieces[g] != 0u) in.load(lo, hi, piece0[g]);
 }
 
 }  // namespace eg
@@ -253,6 +339,73 @@ __global__ void __launch_bounds__(NT, 2) k_gt_encode(u32 n_groups, u32 n_slots, 
 #pragma unroll
     for (int k = 0; k < 8; ++k) tallies[j * 8 + k] = w[k];
     if (t == 0u && out_counts) out_counts[g] = counts[g];
+  }
+}
+
+// ---- the weighted pass: count and fill with the weight check, the level-0 sum with the ladder, the weight sums beside the points ----------
+// (the scan kernels, k_gt_sum_points and k_gt_encode serve it as they are)
+struct GtWeightsDev {
+  const u64* w;
+  u32 n;                 // ballots behind `w`
+  __device__ __forceinline__ u64 load(u32 b) const { return w[b < n ? b : 0u]; }      // clamped as GtWireDev::load, for the same reason
+};
+struct GtSumsDev {
+  u64* base;             // (low, high) per piece
+  __device__ __forceinline__ void store(u32 u, u64 lo, u64 hi) { base[2 * (size_t)u] = lo; base[2 * (size_t)u + 1] = hi; }
+  __device__ __forceinline__ void load(u64& lo, u64& hi, u32 u) const { lo = base[2 * (size_t)u]; hi = base[2 * (size_t)u + 1]; }
+};
+// *ctr += the lanes of the wavefront with `flag`, in one atomic
+__device__ __forceinline__ void gt_wave_tally(u32* ctr, bool flag) {
+  const unsigned long long m = __ballot(flag);
+  if (m && (threadIdx.x & 63) == __ffsll((long long)m) - 1) atomicAdd(ctr, (u32)__popcll(m));
+}
+
+// whole blocks, as k_gt_count / k_gt_fill
+__global__ void __launch_bounds__(NT) k_gtw_count(u32 n, const u32* status, const u32* groups, u32 n_groups, GtWeightsDev weights, int bits,
+                                                  u32* counts, u32* bad) {
+  const u32 b = blockIdx.x * NT + threadIdx.x;
+  u32 g = eggt::GROUP_NONE;
+  const u32 cls = b < n ? gt_weighted_class(g, b, status, groups, n_groups, weights, bits) : 0u;
+  gt_wave_tally(bad, cls == 2u);
+  gt_wave_tally(bad + 2, cls == 3u);
+  (void)pip_wave_atomic_inc(counts, (size_t)g, cls == 1u);
+}
+__global__ void __launch_bounds__(NT) k_gtw_fill(u32 n, const u32* status, const u32* groups, u32 n_groups, GtWeightsDev weights, int bits,
+                                                 const u32* offsets, u32* cursors, u32* idx) {
+  const u32 b = blockIdx.x * NT + threadIdx.x;
+  u32 g = eggt::GROUP_NONE;
+  const bool in = b < n && gt_weighted_class(g, b, status, groups, n_groups, weights, bits) == 1u;
+  const u32 pos = pip_wave_atomic_inc(cursors, (size_t)g, in);
+  const u32 at = in ? offsets[g] + pos : 0u;                       // as k_gt_fill: inside the list unless the caller's words changed meanwhile
+  if (in && at < n) idx[at] = b;
+}
+__global__ void __launch_bounds__(NT, 2) k_gtw_sum_wire(u32 s1, u32 n_slots, GtLevel L, const u32* total, u32 n_groups, const u32* idx,
+                                                        GtWireDev wire, const u32* items, GtWeightsDev weights, int bits, uint4* out, u64* sums,
+                                                        u32* bad) {
+  const size_t lanes = (size_t)*total * n_slots;
+  GtPointsDev o{out};
+  GtSumsDev ws{sums};
+  GtBadDev nb;
+  for (size_t j = (size_t)blockIdx.x * NT + threadIdx.x; j < lanes; j += (size_t)gridDim.x * NT) {
+    const u32 u = (u32)(j / n_slots), t = (u32)(j % n_slots);
+    gt_lane_wire_weighted(u, t, n_slots, s1, L, n_groups, idx, wire, items[t], weights, bits, o, ws, nb);
+  }
+  if (nb.n) atomicAdd(bad + 1, nb.n);
+}
+// one lane = one piece of the level
+__global__ void __launch_bounds__(NT) k_gtw_weight_sums(u32 s2, GtLevel L, const u32* total, u32 n_groups, const u64* in, u64* out) {
+  const u32 pieces = *total;
+  const GtSumsDev i{const_cast<u64*>(in)};
+  GtSumsDev o{out};
+  for (size_t u = (size_t)blockIdx.x * NT + threadIdx.x; u < pieces; u += (size_t)gridDim.x * NT) gt_lane_weight_sums((u32)u, s2, L, n_groups, i, o);
+}
+// pieces / piece0: the last level's; weight_sums: [n_groups][2] 64-bit words
+__global__ void __launch_bounds__(NT) k_gtw_weight_sums_out(u32 n_groups, const u32* pieces, const u32* piece0, const u64* in, u64* weight_sums) {
+  const GtSumsDev i{const_cast<u64*>(in)};
+  for (size_t g = (size_t)blockIdx.x * NT + threadIdx.x; g < n_groups; g += (size_t)gridDim.x * NT) {
+    u64 lo, hi;
+    gt_lane_weight_sum_out(lo, hi, (u32)g, pieces, piece0, i);
+    weight_sums[2 * g] = lo; weight_sums[2 * g + 1] = hi;
   }
 }
 

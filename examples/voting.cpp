@@ -1,7 +1,7 @@
 // voting.cpp -- the reference's examples/voting.rs on the GPU backend, in C++ on top of the C ABI:
 //   `Args::vote`            (examples/voting.rs:179-213)  ./voting [votes] [options] [seed]
 //   `Args::quadratic_vote`  (examples/voting.rs:219-269)  ./voting --qv [votes] [options] [credits] [seed]
-//   options: --devices N, --json, --precincts P
+//   options: --devices N, --json, --precincts P, --weighted
 // talliers' key -> voters create ballots from their own choices -> verify every ballot -> homomorphic totals -> decrypt and
 // compare with the EXPECTED totals the voters' choices add up to.  Threshold sharing of the key (examples/voting.rs:105-120) is out
 // of scope; a single key pair stands in for the shared key (tests/test_gpu_parity.py::test_threshold_tally_end_to_end
@@ -11,6 +11,9 @@
 // (JsonStream = eg_verify_choice_json_begin / eg_verify_json_feed / _end), which cuts, packs and verifies them as they arrive.
 // With --precincts P voter v belongs to precinct v mod P: after the overall totals, the per-precinct totals of the same verified batch
 // (tally_grouped = eg_*_tally_grouped, one pass over the accepted ballots) are decrypted the same way and must add up to the overall result.
+// With --weighted voter v also holds a weight (shares, stake): 1 + 7919 v mod 65535.  The weighted totals of the same verified batch
+// (tally_weighted = eg_*_tally_weighted: total += ciphertext * weight, the reference's impl Mul<u64> for Ciphertext) are decrypted and read
+// with the discrete-log solver over [0, sum of the counted weights x most votes per option] - the table above would not reach that far.
 //
 //   g++ -std=c++17 -Iinclude examples/voting.cpp -Lelastic_elgamal_amd -leg_hip -Wl,-rpath,$PWD/elastic_elgamal_amd -o voting
 #include <cstdio>
@@ -76,6 +79,42 @@ static bool precinct_tally(const Context& ctx, const Ristretto& group, const Sca
   return ok;
 }
 
+// --weighted: every accepted ballot counts weight(v) times; votes_of[v * options + k] = what voter v gave option k
+static uint64_t weight_of(size_t v) { return 1 + (7919 * (uint64_t)v) % 65535; }
+template <class Params, class Verdict>
+static bool weighted_tally(const Context& ctx, const Ristretto& group, const Scalar& sk, const Params& params, const Bytes& ballots,
+                           const Verdict& verdict, const std::vector<uint32_t>& votes_of, size_t options, uint64_t max_per_option) {
+  const size_t votes = verdict.results.size();
+  std::vector<uint32_t> status(votes);
+  std::vector<uint64_t> weights(votes), expected(options, 0);
+  for (size_t v = 0; v < votes; ++v) {
+    status[v] = verdict.results[v] ? 1u : 0u;
+    weights[v] = weight_of(v);
+    printf("weighted voter #%zu: weight %llu, votes", v + 1, (unsigned long long)weights[v]);
+    for (size_t k = 0; k < options; ++k) {
+      printf(" %u", votes_of[v * options + k]);
+      if (!status[v]) expected[k] += weights[v] * votes_of[v * options + k];
+    }
+    printf(", %s\n", status[v] ? "rejected" : "accepted");
+  }
+  const WeightedTally w = params.tally_weighted(ballots, status, weights, 16);          // one group: every ballot
+  if (w.weight_sums[0].high) { printf("the weights add up to more than 64 bits\n"); return false; }
+  const uint64_t weight_sum = w.weight_sums[0].low;
+  printf("sum of the counted weights: %llu\n", (unsigned long long)weight_sum);
+  std::vector<Element> decrypted;
+  for (const Ciphertext& c : w.totals[0]) decrypted.push_back(group.sub(c.blinded_element, group.mul(c.random_element, sk)));
+  const DiscreteLogSolver solver(ctx);
+  const std::vector<std::optional<uint64_t>> found = solver.solve(decrypted, 0, weight_sum * max_per_option);
+  bool ok = w.accepted[0] == verdict.accepted();
+  for (size_t k = 0; k < options; ++k) {
+    if (!found[k]) { printf("weighted total of option #%zu: not found\n", k + 1); ok = false; continue; }
+    printf("weighted total of option #%zu: %llu\n", k + 1, (unsigned long long)*found[k]);
+    ok = ok && *found[k] == expected[k];
+  }
+  printf("%s: the decrypted weighted totals %s the expected ones\n", ok ? "OK" : "MISMATCH", ok ? "equal" : "differ from");
+  return ok;
+}
+
 // serde's human-readable form of an EncryptedChoice (src/serde.rs:19-80: every element and scalar as unpadded base64url; field names of
 // choice.rs:276-280, ring.rs:282-287, log_equality.rs:96-101), from the packed ballot
 static std::string b64url(const uint8_t* p, size_t n) {
@@ -101,13 +140,14 @@ static std::string choice_to_json(const uint8_t* b, size_t options) {
 }
 
 int main(int argc, char** argv) {
-  bool qv = false, json = false;
+  bool qv = false, json = false, weighted = false;
   int devices = 1;
   long precincts = 0;
   std::vector<std::string> pos;
   for (int i = 1; i < argc; ++i) {
     if (!strcmp(argv[i], "--qv")) qv = true;
     else if (!strcmp(argv[i], "--json")) json = true;
+    else if (!strcmp(argv[i], "--weighted")) weighted = true;
     else if (!strcmp(argv[i], "--devices") && i + 1 < argc) devices = atoi(argv[++i]);
     else if (!strcmp(argv[i], "--precincts") && i + 1 < argc) precincts = atol(argv[++i]);
     else pos.push_back(argv[i]);
@@ -173,6 +213,11 @@ int main(int argc, char** argv) {
       if (verdict.results[i]) printf("  voter #%zu rejected: %s\n", i + 1, verdict.results[i]->to_string().c_str());
     ok = verdict.accepted() == votes - (forged < votes ? 1 : 0) && tally(ctx, group, sk, verdict.totals, expected, votes);
     if (precincts) ok = precinct_tally(ctx, group, sk, *params[0], ballots, verdict, (uint32_t)precincts, expected_by_precinct, expected, votes) && ok;
+    if (weighted) {
+      std::vector<uint32_t> one_hot(votes * options, 0u);
+      for (size_t i = 0; i < votes; ++i) one_hot[i * options + choices[i]] = 1u;
+      ok = weighted_tally(ctx, group, sk, *params[0], ballots, verdict, one_hot, options, 1) && ok;
+    }
   } else {
     std::vector<std::unique_ptr<QuadraticVotingParams>> params;
     for (auto& c : ctxs) params.push_back(std::make_unique<QuadraticVotingParams>(*c, pk, options, credits));
@@ -203,6 +248,7 @@ int main(int argc, char** argv) {
     const uint64_t max_votes = votes * params[0]->max_votes();                          // votes_count * vote_params.max_votes()
     ok = verdict.accepted() == votes - (forged < votes ? 1 : 0) && tally(ctx, group, sk, verdict.totals, expected, max_votes);
     if (precincts) ok = precinct_tally(ctx, group, sk, *params[0], ballots, verdict, (uint32_t)precincts, expected_by_precinct, expected, max_votes) && ok;
+    if (weighted) ok = weighted_tally(ctx, group, sk, *params[0], ballots, verdict, all, options, params[0]->max_votes()) && ok;
   }
   printf("%s: the decrypted totals %s the expected ones\n", ok ? "OK" : "MISMATCH", ok ? "equal" : "differ from");
   return ok ? 0 : 1;

@@ -348,6 +348,48 @@ int eg_qv_tally_grouped_device(eg_qv_params*, size_t n, const void* d_ballots, c
 int eg_qv_tally_grouped(eg_qv_params*, size_t n, const uint8_t* ballots, const uint32_t* status, const uint32_t* groups,
                         uint32_t n_groups, uint8_t* tallies, uint32_t* counts /* may be NULL */);
 
+/* ---- weighted per-group tally: every accepted ballot counts with a weight of its own (shares, stake, delegated votes) ----------------
+ * The reference's Ciphertext has scalar multiplication beside Add and Sub (impl Mul<u64>, src/encryption.rs:197-215); a host that holds
+ * one ballot per voter weights votes with `total += ballot.ciphertext * w`.  These entries are the per-group tally above with that
+ * product inside: tallies[g][t] = the canonical encoding of the sum of [weights[b]] x (tally point t of ballot b) over the ballots with
+ * status[b] == 0, groups[b] == g and weights[b] < 2^weight_bits; 32 zero bytes for an empty sum.  The layout is the grouped entry's.  With
+ * every weight 1 the output is byte for byte that of eg_*_tally_grouped.  A weight of 0 is valid: the ballot counts in counts[g] and adds
+ * nothing.  groups == NULL puts every ballot into group 0 (n_groups must then be 1).
+ * weight_bits (1..64) is the caller's bound on the bit length of a weight.  It fixes the length of every lane's doubling chain for the
+ * whole call - 16-bit weights cost 16 doublings per point, not 64 - so it should be as small as the weights allow.
+ * weight_sums[g] (optional, two uint64 per group: low word, high word) = the exact sum of the counted weights of group g.  No tally
+ * counter can exceed it: it is the upper bound to hand to eg_dlog_solver_solve when the totals are decrypted.  counts[g] as above.
+ *
+ * UNTRUSTED INPUTS.  The library WRITES the three words of `bad`: bad[0] and bad[1] as in the grouped entry; bad[2] = accepted ballots
+ * with a group id in range whose weight is 2^weight_bits or more (never with weight_bits == 64).  Such a ballot is left out of tallies,
+ * counts and weight sums alike.  If any word is non-zero the results are to be discarded; the host form then returns EG_ERR_BAD_ARG.
+ * Ids and weights of REJECTED ballots are never read.
+ * EG_ERR_BAD_ARG before anything is launched: everything the grouped entry refuses, weight_bits outside 1..64, NULL weights with n > 0,
+ * NULL groups with n_groups != 1, weights or weight sums that are not 8-byte aligned.  n == 0 is valid: all-zero tallies, sums, counts.
+ *
+ * STATELESS as the grouped pass: the params object's immutable plan only - no lock, no workspace, no running tally.  The `_device`
+ * form is asynchronous on `stream` and allocates nothing; d_scratch holds eg_*_tally_weighted_scratch_bytes(params, n, n_groups) bytes
+ * (0 for arguments that would be refused): the grouped pass's scratch and 16 bytes per partial sum of slot 0 for the weight sums.
+ * MERGING.  Weighted tallies of slabs or ranks merge with eg_points_sum_device like grouped ones, weight sums and counts by addition. */
+size_t eg_choice_tally_weighted_scratch_bytes(const eg_choice_params*, size_t n, uint32_t n_groups);
+int eg_choice_tally_weighted_device(eg_choice_params*, size_t n, const void* d_ballots, const void* d_status,
+                                    const void* d_weights /* n x uint64 */, int weight_bits /* 1..64 */,
+                                    const void* d_groups /* NULL: every ballot in group 0, n_groups must be 1 */, uint32_t n_groups,
+                                    void* d_scratch, void* d_tallies, void* d_weight_sums /* n_groups x 2 x uint64 (low, high), may be NULL */,
+                                    void* d_counts /* may be NULL */, void* d_bad /* 3 x uint32 */, void* stream);
+int eg_choice_tally_weighted(eg_choice_params*, size_t n, const uint8_t* ballots, const uint32_t* status, const uint64_t* weights,
+                             int weight_bits, const uint32_t* groups /* may be NULL */, uint32_t n_groups, uint8_t* tallies,
+                             uint64_t* weight_sums /* may be NULL */, uint32_t* counts /* may be NULL */);
+size_t eg_qv_tally_weighted_scratch_bytes(const eg_qv_params*, size_t n, uint32_t n_groups);
+int eg_qv_tally_weighted_device(eg_qv_params*, size_t n, const void* d_ballots, const void* d_status,
+                                const void* d_weights /* n x uint64 */, int weight_bits /* 1..64 */,
+                                const void* d_groups /* NULL: every ballot in group 0, n_groups must be 1 */, uint32_t n_groups,
+                                void* d_scratch, void* d_tallies, void* d_weight_sums /* n_groups x 2 x uint64 (low, high), may be NULL */,
+                                void* d_counts /* may be NULL */, void* d_bad /* 3 x uint32 */, void* stream);
+int eg_qv_tally_weighted(eg_qv_params*, size_t n, const uint8_t* ballots, const uint32_t* status, const uint64_t* weights,
+                         int weight_bits, const uint32_t* groups /* may be NULL */, uint32_t n_groups, uint8_t* tallies,
+                         uint64_t* weight_sums /* may be NULL */, uint32_t* counts /* may be NULL */);
+
 /* ---- batch tier on several GPUs of ONE process (SURVEY.md 8b `device_mask`; the reference's host is one single-threaded process,
  * examples/voting.rs:179-213) -----------------------------------------------------------------------------------------------------
  * per_device[d], d < n_dev: params objects of the SAME election (same key, options, kind), each created on its own context

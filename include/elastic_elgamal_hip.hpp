@@ -130,6 +130,23 @@ inline GroupedTally unpack_grouped(const Bytes& t, std::vector<uint32_t> counts,
   return g;
 }
 
+// Weighted per-group tally (eg_*_tally_weighted): totals[g] = the sum of weight x ciphertext over the accepted ballots of group g;
+// weight_sums[g] = the exact sum of their weights, a 128-bit number (the bound for the discrete-log solver); accepted[g] as above.
+struct WeightSum { uint64_t low, high; };
+struct WeightedTally {
+  std::vector<std::vector<Ciphertext>> totals;
+  std::vector<WeightSum> weight_sums;
+  std::vector<uint32_t> accepted;
+};
+inline WeightedTally unpack_weighted(const Bytes& t, const std::vector<uint64_t>& sums, std::vector<uint32_t> counts, size_t options) {
+  GroupedTally g = unpack_grouped(t, std::move(counts), options);
+  WeightedTally w;
+  w.totals = std::move(g.totals);
+  w.accepted = std::move(g.accepted);
+  for (size_t k = 0; k < w.accepted.size(); ++k) w.weight_sums.push_back(WeightSum{sums[2 * k], sums[2 * k + 1]});
+  return w;
+}
+
 // ChoiceParams<G, S> (choice.rs:132-196); S is SingleChoice (sum proof) or MultiChoice
 class ChoiceParams {
  public:
@@ -189,6 +206,28 @@ class ChoiceParams {
   void tally_grouped_device(size_t n, const void* d_ballots, const void* d_status, const void* d_groups, uint32_t n_groups, void* d_scratch,
                             void* d_tallies, void* d_counts, void* d_bad, void* stream = nullptr) const {
     check(eg_choice_tally_grouped_device(p_, n, d_ballots, d_status, d_groups, n_groups, d_scratch, d_tallies, d_counts, d_bad, stream));
+  }
+  // weighted form: weights[b] < 2^weight_bits times the ciphertexts of ballot b; an empty `groups` puts every ballot into one group
+  WeightedTally tally_weighted(const Bytes& packed, const std::vector<uint32_t>& status, const std::vector<uint64_t>& weights, int weight_bits,
+                               const std::vector<uint32_t>& groups = {}, uint32_t n_groups = 1) const {
+    const size_t n = packed.size() / ballot_size();
+    if (n * ballot_size() != packed.size() || status.size() != n || weights.size() != n || (!groups.empty() && groups.size() != n))
+      throw Error(EG_ERR_BAD_ARG, "packed, status, weights and groups do not describe the same number of ballots");
+    if (n_groups == 0 || n_groups > EG_TALLY_GROUPS_MAX) throw Error(EG_ERR_BAD_ARG, "n_groups out of range");
+    Bytes tallies((size_t)n_groups * 64 * n_);
+    std::vector<uint64_t> sums(2 * (size_t)n_groups);
+    std::vector<uint32_t> counts(n_groups);
+    check(eg_choice_tally_weighted(p_, n, packed.data(), status.data(), weights.data(), weight_bits, groups.empty() ? nullptr : groups.data(),
+          n_groups, tallies.data(), sums.data(), counts.data()));
+    return unpack_weighted(tallies, sums, std::move(counts), n_);
+  }
+  // asynchronous device-pointer form: d_scratch of tally_weighted_scratch_bytes(n, n_groups) bytes, d_bad three uint32 the library writes
+  size_t tally_weighted_scratch_bytes(size_t n, uint32_t n_groups) const { return eg_choice_tally_weighted_scratch_bytes(p_, n, n_groups); }
+  void tally_weighted_device(size_t n, const void* d_ballots, const void* d_status, const void* d_weights, int weight_bits, const void* d_groups,
+                             uint32_t n_groups, void* d_scratch, void* d_tallies, void* d_weight_sums, void* d_counts, void* d_bad,
+                             void* stream = nullptr) const {
+    check(eg_choice_tally_weighted_device(p_, n, d_ballots, d_status, d_weights, weight_bits, d_groups, n_groups, d_scratch, d_tallies,
+          d_weight_sums, d_counts, d_bad, stream));
   }
   // EncryptedChoice::new for synthetic voters base_seed + first + i (choice.rs:313-349), packed
   Bytes encrypt_batch(uint64_t base_seed, size_t first, size_t n, int n_selected = 0) const {
@@ -275,6 +314,28 @@ class QuadraticVotingParams {
   void tally_grouped_device(size_t n, const void* d_ballots, const void* d_status, const void* d_groups, uint32_t n_groups, void* d_scratch,
                             void* d_tallies, void* d_counts, void* d_bad, void* stream = nullptr) const {
     check(eg_qv_tally_grouped_device(p_, n, d_ballots, d_status, d_groups, n_groups, d_scratch, d_tallies, d_counts, d_bad, stream));
+  }
+  // weighted form: weights[b] < 2^weight_bits times the ciphertexts of ballot b; an empty `groups` puts every ballot into one group
+  WeightedTally tally_weighted(const Bytes& packed, const std::vector<uint32_t>& status, const std::vector<uint64_t>& weights, int weight_bits,
+                               const std::vector<uint32_t>& groups = {}, uint32_t n_groups = 1) const {
+    const size_t n = packed.size() / ballot_size();
+    if (n * ballot_size() != packed.size() || status.size() != n || weights.size() != n || (!groups.empty() && groups.size() != n))
+      throw Error(EG_ERR_BAD_ARG, "packed, status, weights and groups do not describe the same number of ballots");
+    if (n_groups == 0 || n_groups > EG_TALLY_GROUPS_MAX) throw Error(EG_ERR_BAD_ARG, "n_groups out of range");
+    Bytes tallies((size_t)n_groups * 64 * n_);
+    std::vector<uint64_t> sums(2 * (size_t)n_groups);
+    std::vector<uint32_t> counts(n_groups);
+    check(eg_qv_tally_weighted(p_, n, packed.data(), status.data(), weights.data(), weight_bits, groups.empty() ? nullptr : groups.data(),
+          n_groups, tallies.data(), sums.data(), counts.data()));
+    return unpack_weighted(tallies, sums, std::move(counts), n_);
+  }
+  // asynchronous device-pointer form: d_scratch of tally_weighted_scratch_bytes(n, n_groups) bytes, d_bad three uint32 the library writes
+  size_t tally_weighted_scratch_bytes(size_t n, uint32_t n_groups) const { return eg_qv_tally_weighted_scratch_bytes(p_, n, n_groups); }
+  void tally_weighted_device(size_t n, const void* d_ballots, const void* d_status, const void* d_weights, int weight_bits, const void* d_groups,
+                             uint32_t n_groups, void* d_scratch, void* d_tallies, void* d_weight_sums, void* d_counts, void* d_bad,
+                             void* stream = nullptr) const {
+    check(eg_qv_tally_weighted_device(p_, n, d_ballots, d_status, d_weights, weight_bits, d_groups, n_groups, d_scratch, d_tallies,
+          d_weight_sums, d_counts, d_bad, stream));
   }
   // QuadraticVotingBallot::new(&params, votes, rng) for voters base_seed + first + i (quadratic_voting.rs:234-284); votes:
   // options_count() numbers per voter with sum(v^2) <= credits.  VARIABLE TIME in the votes (see eg_hip.h): test / synthetic data only.
