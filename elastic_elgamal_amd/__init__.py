@@ -137,6 +137,10 @@ def _load() -> C.CDLL:
         "eg_choice_prepare_wide_tables": (C.c_int, [vp]),
         "eg_qv_prepare_wide_tables": (C.c_int, [vp]),
         "eg_combine_shares": (C.c_int, [vp, C.c_uint64, C.c_uint64, sz, C.POINTER(C.c_uint64), cp, cp, C.POINTER(C.c_int)]),
+        "eg_combine_shares_batch_scratch_bytes": (sz, [C.c_uint64, sz]),
+        "eg_combine_shares_batch_device": (C.c_int, [vp, C.c_uint64, C.c_uint64, sz, vp, C.c_int, C.POINTER(C.c_uint64), vp, vp, vp, vp, vp, vp, vp,
+                                                     vp, vp]),
+        "eg_combine_shares_batch": (C.c_int, [vp, C.c_uint64, C.c_uint64, sz, vp, C.c_int, C.POINTER(C.c_uint64), vp, vp, vp, vp, vp, vp]),
         "eg_dlog_table_create": (C.c_int, [vp, sz, C.POINTER(C.c_uint64), C.POINTER(vp)]),
         "eg_dlog_table_destroy": (None, [vp]),
         "eg_dlog_table_get": (C.c_int, [vp, sz, cp, C.POINTER(C.c_uint64), cp]),

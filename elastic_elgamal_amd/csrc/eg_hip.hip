@@ -31,6 +31,7 @@
 #include "pippenger.cuh"
 #include "dlog_kernels.cuh"
 #include "group_tally_kernels.cuh"
+#include "share_combine_kernels.cuh"
 
 using namespace eg;
 
@@ -1679,6 +1680,98 @@ int eg_combine_shares(eg_ctx* c, uint64_t shares, uint64_t threshold, size_t n, 
   TRY(eg_vartime_multi_mul_batch(c, 1, t, coeff.data(), dh_elements, out, &ok));
   if (!ok) return fail(EG_ERR_BAD_ARG, "a decryption share is not a valid ristretto255 encoding");
   *combined = 1;
+  return EG_OK;
+}
+
+// ---- shares of many ciphertexts in one pass (share_combine_kernels.cuh; layout and argument rules: share_combine_host.hpp) ---------------
+// Params::combine_shares and VerifiableDecryption::decrypt_to_element for a whole vector of ciphertexts: per-precinct tallies are 10^4 ..
+// 10^5 of them, and eg_combine_shares opens one per dozen synchronised calls.  Stateless like the grouped tally: no lock, no workspace of
+// the context (only its device number is read), scratch from the caller, three launches per slab of ciphertexts on the caller's stream.
+static int combine_batch_check(uint64_t shares, uint64_t threshold, size_t m, int k, const uint64_t* indexes) {
+  const char* why = egsc::refuse_sizes(shares, threshold, m);
+  if (!why) why = egsc::refuse_columns(shares, k, indexes);
+  if (why) return fail(EG_ERR_BAD_ARG, std::string("share combine: ") + why);
+  return EG_OK;
+}
+size_t eg_combine_shares_batch_scratch_bytes(uint64_t threshold, size_t m) { return egsc::scratch_bytes(threshold, m); }
+int eg_combine_shares_batch_device(eg_ctx* c, uint64_t shares, uint64_t threshold, size_t m, const void* d_ciphertexts, int k,
+                                   const uint64_t* indexes, const void* d_items, const void* d_status, void* d_dh, void* d_plain,
+                                   void* d_combined, void* d_used, void* d_bad, void* d_scratch, void* stream) {
+  TRY_(combine_batch_check(shares, threshold, m, k, indexes));
+  if (m && (!d_ciphertexts || (k && !d_items) || !d_combined || !d_bad)) return fail(EG_ERR_BAD_ARG, "share combine: null device pointer");
+  if (egsc::scratch_bytes(threshold, m) && !d_scratch)
+    return fail(EG_ERR_BAD_ARG, "share combine: null scratch (eg_combine_shares_batch_scratch_bytes says how much)");
+  if (((uintptr_t)d_ciphertexts | (uintptr_t)d_items | (uintptr_t)d_status | (uintptr_t)d_dh | (uintptr_t)d_plain | (uintptr_t)d_combined |
+       (uintptr_t)d_bad | (uintptr_t)d_scratch) & 15u)
+    return fail(EG_ERR_BAD_ARG, "share combine: device buffers must be 16-byte aligned");
+  if ((uintptr_t)d_used & 7u) return fail(EG_ERR_BAD_ARG, "share combine: d_used must be 8-byte aligned");
+  if (!c) return fail(EG_ERR_BAD_ARG, "share combine: null context");
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)stream;
+  u32* bad = static_cast<u32*>(d_bad);
+  if (bad) HIPCHK(hipMemsetAsync(bad, 0, 3 * sizeof(u32), s));
+  if (m == 0) return EG_OK;
+  const egsc::Layout L = egsc::layout(threshold, m);
+  char* base = static_cast<char*>(d_scratch);
+  u64* masks = reinterpret_cast<u64*>(base + L.mask);
+  u32* coef = reinterpret_cast<u32*>(base + L.coef);
+  uint4* tables = reinterpret_cast<uint4*>(base + L.tables);
+  ScIndexes idx{};
+  for (int j = 0; j < k; ++j) idx.v[j] = (unsigned char)indexes[j];
+  const ScStatusDev status{static_cast<const u32*>(d_status), m};
+  const ScItemsDev items{static_cast<const uint4*>(d_items), m};
+  const ScCtDev cts{static_cast<const uint4*>(d_ciphertexts)};
+  const u32 t = (u32)threshold;
+  for (size_t first = 0; first < m; first += L.lanes) {
+    const u32 count = (u32)std::min(L.lanes, m - first);
+    const dim3 grid((count + NT - 1) / NT);
+    hipLaunchKernelGGL(k_sc_select, grid, dim3(NT), 0, s, (u32)first, count, k, t, status, items, cts, masks, bad);
+    if ((uint64_t)k >= threshold) hipLaunchKernelGGL(k_sc_coeffs, grid, dim3(NT), 0, s, count, k, t, idx, (const u64*)masks, coef, L.lanes);
+    hipLaunchKernelGGL(k_sc_combine, grid, dim3(NT), 0, s, (u32)first, count, k, t, L.chunk, idx, items, cts, (const u64*)masks, (const u32*)coef,
+                       L.lanes, tables, d_dh, d_plain, static_cast<unsigned char*>(d_combined), static_cast<u64*>(d_used), bad);
+  }
+  HIPCHK(hipGetLastError());
+  return EG_OK;
+}
+// host buffers, staged into device memory of the call's own
+int eg_combine_shares_batch(eg_ctx* c, uint64_t shares, uint64_t threshold, size_t m, const uint8_t* ciphertexts, int k, const uint64_t* indexes,
+                            const uint8_t* items, const uint32_t* status, uint8_t* dh, uint8_t* plain, uint8_t* combined, uint64_t* used) {
+  TRY_(combine_batch_check(shares, threshold, m, k, indexes));
+  if (m && (!ciphertexts || (k && !items) || !combined)) return fail(EG_ERR_BAD_ARG, "share combine: null pointer");
+  if (!c) return fail(EG_ERR_BAD_ARG, "share combine: null context");
+  if (m == 0) return EG_OK;
+  HIPCHK(hipSetDevice(c->device));
+  enum { CTS, ITEMS, STATUS, DH, PLAIN, COMBINED, USED, BAD, SCRATCH, N_BUF };
+  const size_t sizes[N_BUF] = {m * 64, (size_t)k * m * 128, status ? (size_t)k * m * 4 : 0, m * 32, m * 32, m, m * 8, 16,
+                               egsc::scratch_bytes(threshold, m)};
+  void* d[N_BUF] = {};
+  hipStream_t s = nullptr;
+  ScopeExit release{[&]() {
+    for (void* p : d) if (p) (void)hipFree(p);
+    if (s) (void)hipStreamDestroy(s);
+  }};
+  for (int b = 0; b < N_BUF; ++b) {
+    const hipError_t he = hipMalloc(&d[b], std::max<size_t>(sizes[b], 16));
+    if (he == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(EG_ERR_NOMEM, "share combine: the staging buffers do not fit the device memory"); }
+    HIPCHK(he);
+  }
+  HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+  HIPCHK(hipMemcpyAsync(d[CTS], ciphertexts, sizes[CTS], hipMemcpyHostToDevice, s));
+  if (k) HIPCHK(hipMemcpyAsync(d[ITEMS], items, sizes[ITEMS], hipMemcpyHostToDevice, s));
+  if (k && status) HIPCHK(hipMemcpyAsync(d[STATUS], status, sizes[STATUS], hipMemcpyHostToDevice, s));
+  TRY_(eg_combine_shares_batch_device(c, shares, threshold, m, d[CTS], k, indexes, d[ITEMS], status ? d[STATUS] : nullptr, d[DH], d[PLAIN],
+                                      d[COMBINED], d[USED], d[BAD], d[SCRATCH], s));
+  u32 bad[3] = {0, 0, 0};
+  if (dh) HIPCHK(hipMemcpyAsync(dh, d[DH], sizes[DH], hipMemcpyDeviceToHost, s));
+  if (plain) HIPCHK(hipMemcpyAsync(plain, d[PLAIN], sizes[PLAIN], hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(combined, d[COMBINED], sizes[COMBINED], hipMemcpyDeviceToHost, s));
+  if (used) HIPCHK(hipMemcpyAsync(used, d[USED], sizes[USED], hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(bad, d[BAD], sizeof bad, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  if (bad[0] || bad[1] || bad[2])
+    return fail(EG_ERR_BAD_ARG, "share combine: " + std::to_string(bad[0]) + " accepted share(s) proven for another ciphertext, " +
+                                    std::to_string(bad[1]) + " chosen share(s) that do not decode, " + std::to_string(bad[2]) +
+                                    " ciphertext(s) whose blinded element does not decode");
   return EG_OK;
 }
 

@@ -203,6 +203,47 @@ int eg_vartime_multi_mul_prepared_batch_device(eg_ctx*, size_t n, size_t terms, 
  * group arithmetic runs on the GPU primitives. */
 int eg_combine_shares(eg_ctx*, uint64_t shares, uint64_t threshold, size_t n, const uint64_t* indexes, const uint8_t* dh_elements,
                       uint8_t out[32], int* combined);
+/* The same for a whole VECTOR of ciphertexts in one pass (csrc/share_combine_kernels.cuh): the step between "shares verified" and
+ * "element handed to the discrete-log solver" for per-precinct tallies, which are 10^4 .. 10^5 ciphertexts where eg_combine_shares
+ * opens one per call.  The k columns are participants: column j holds participant indexes[j]'s m items in the 128-byte layout that
+ * eg_share_prove_batch writes and eg_verify_proof_batch reads (R || dh || challenge || response), item c belonging to ciphertext c, and
+ * (optionally) the m status words the verify entry wrote for them - a caller verifies each participant's column into its slice of one
+ * buffer and passes the buffers on without a copy.
+ * PER CIPHERTEXT c the columns are walked in the caller's order.  Column j is usable when its status word is EG_ST_OK (d_status NULL:
+ * every share counts as accepted) AND the first 32 bytes of its item equal the first 32 bytes of ciphertext c: a share proven for another
+ * ciphertext is never combined into this one (the reference binds R through the `ciphertext` argument of verify_share).  The first
+ * `threshold` usable columns are the shares (`.take(self.threshold)`); columns behind them are not looked at.  Fewer than `threshold`
+ * usable columns: combined[c] = 0, 32 zero bytes in dh and plain, used[c] = 0 (the reference's None).  Otherwise
+ * D = [scale] sum [denominator_j^-1] dh_j with the reference's signed denominators and scale, dh[c] = serialize(D),
+ * plain[c] = serialize(B - D) - the element eg_dlog_solver_solve and eg_dlog_table_get take -, combined[c] = 1, and used[c] has bit
+ * indexes[j] set for every share used.  Encodings are canonical, so the output is a function of the chosen shares alone and equals
+ * eg_combine_shares + eg_point_add_batch on them byte for byte.
+ * UNTRUSTED INPUTS.  The library WRITES the three words of `bad`: bad[0] = shares marked accepted, met on the walk, whose R bytes are
+ * not the ciphertext's (skipped, the walk goes on); bad[1] = chosen shares whose dh does not decode; bad[2] = ciphertexts whose B does
+ * not decode (counted only when d_plain is given).  For bad[1] and bad[2] the ciphertext gets combined = 0 and zero bytes; the call
+ * still returns EG_OK.  Shares of columns that are not accepted are never decoded.  The host form returns EG_ERR_BAD_ARG when any word is
+ * non-zero, AFTER writing its outputs.
+ * EG_ERR_BAD_ARG before anything is launched: shares of 0 or above EG_COMBINE_SHARES_MAX, threshold outside 1..shares, k < 0 or k >
+ * shares, an index >= shares, a duplicate index, m >= 2^31, a NULL d_ciphertexts / d_items / d_combined / d_bad / indexes with m > 0 (and
+ * k > 0), NULL scratch when the size is not 0, buffers that are not 16-byte aligned (d_used: 8-byte).  k < threshold is valid: every
+ * combined is 0.  m == 0 is valid.
+ * STATELESS like the grouped tally: no lock, no workspace of the context, nothing allocated; the `_device` form is asynchronous on
+ * `stream` and never synchronises with the host.  d_scratch holds eg_combine_shares_batch_scratch_bytes(threshold, m) bytes (0 for
+ * arguments that would be refused; it stops growing at 2^17 ciphertexts, which longer vectors pass through one slab after the other).
+ * The host form stages into device memory of its own and returns when the results are written; dh, plain and used may be NULL. */
+#define EG_COMBINE_SHARES_MAX 64      /* participants of a key set the batch entries accept */
+size_t eg_combine_shares_batch_scratch_bytes(uint64_t threshold, size_t m);
+int eg_combine_shares_batch_device(eg_ctx*, uint64_t shares, uint64_t threshold, size_t m,
+                                   const void* d_ciphertexts /* m x 64: R || B */,
+                                   int k, const uint64_t* indexes /* HOST, k zero-based participant indexes */,
+                                   const void* d_items /* k x m x 128, column j at j*m*128: R || dh || challenge || response */,
+                                   const void* d_status /* k x m uint32, column j at j*m; NULL = every share accepted */,
+                                   void* d_dh /* m x 32 or NULL */, void* d_plain /* m x 32 or NULL */,
+                                   void* d_combined /* m bytes */, void* d_used /* m x uint64 or NULL */,
+                                   void* d_bad /* 3 x uint32 */, void* d_scratch, void* stream);
+int eg_combine_shares_batch(eg_ctx*, uint64_t shares, uint64_t threshold, size_t m, const uint8_t* ciphertexts,
+                            int k, const uint64_t* indexes, const uint8_t* items, const uint32_t* status /* may be NULL */,
+                            uint8_t* dh, uint8_t* plain, uint8_t* combined, uint64_t* used);
 /* DiscreteLogTable (src/encryption.rs:260-298): new(values) computes [v]G for every non-zero value on the GPU; get() looks decrypted
  * elements up (found[i] = 0: not among the values; the identity is always 0).  The table itself lives in host memory. */
 typedef struct eg_dlog_table eg_dlog_table;

@@ -699,6 +699,35 @@ inline std::optional<Element> combine_shares(const Context& ctx, uint64_t shares
   check(eg_combine_shares(ctx.raw(), shares, threshold, idx.size(), idx.data(), dh.data(), out.data(), &combined));
   return combined ? std::optional<Element>(out) : std::nullopt;
 }
+// The same for a whole vector of ciphertexts in one pass (eg_combine_shares_batch): column j holds participant indexes[j]'s m items
+// (128 bytes each: R || dh || challenge || response) and, in `status`, the verdicts of its DecryptionShares::verify_batch (empty: every
+// share accepted).  Per ciphertext the first `threshold` usable columns are combined: dh = [x]R, plain = B - [x]R (what the discrete-log
+// solver takes), combined = 0 where there were too few (zero bytes then), used = bit i for every participant i whose share was used.
+struct CombinedShares {
+  std::vector<Element> dh, plain;
+  std::vector<uint8_t> combined;
+  std::vector<uint64_t> used;
+};
+inline CombinedShares combine_shares_batch(const Context& ctx, uint64_t shares, uint64_t threshold, const Bytes& ciphertexts,
+                                           const std::vector<uint64_t>& indexes, const Bytes& items, const std::vector<uint32_t>& status = {}) {
+  const size_t m = ciphertexts.size() / 64, k = indexes.size();
+  if (m * 64 != ciphertexts.size() || items.size() != k * m * 128 || (!status.empty() && status.size() != k * m))
+    throw Error(EG_ERR_BAD_ARG, "ciphertexts, indexes, items and status do not describe the same columns");
+  CombinedShares r;
+  r.dh.resize(m); r.plain.resize(m); r.combined.resize(m); r.used.resize(m);
+  check(eg_combine_shares_batch(ctx.raw(), shares, threshold, m, ciphertexts.data(), (int)k, indexes.data(), items.data(),
+        status.empty() ? nullptr : status.data(), reinterpret_cast<uint8_t*>(r.dh.data()), reinterpret_cast<uint8_t*>(r.plain.data()),
+        r.combined.data(), r.used.data()));
+  return r;
+}
+// asynchronous device-pointer form: d_scratch of combine_shares_batch_scratch_bytes(threshold, m) bytes, d_bad three uint32 the library writes
+inline size_t combine_shares_batch_scratch_bytes(uint64_t threshold, size_t m) { return eg_combine_shares_batch_scratch_bytes(threshold, m); }
+inline void combine_shares_batch_device(const Context& ctx, uint64_t shares, uint64_t threshold, size_t m, const void* d_ciphertexts,
+                                        const std::vector<uint64_t>& indexes, const void* d_items, const void* d_status, void* d_dh,
+                                        void* d_plain, void* d_combined, void* d_used, void* d_bad, void* d_scratch, void* stream = nullptr) {
+  check(eg_combine_shares_batch_device(ctx.raw(), shares, threshold, m, d_ciphertexts, (int)indexes.size(), indexes.data(), d_items, d_status,
+        d_dh, d_plain, d_combined, d_used, d_bad, d_scratch, stream));
+}
 // DiscreteLogTable (encryption.rs:260-298)
 class DiscreteLogTable {
  public:
@@ -737,5 +766,36 @@ class DiscreteLogSolver {
  private:
   eg_dlog_solver* s_ = nullptr;
 };
+
+// The tally stage for a whole vector of ciphertexts (per-precinct tallies): every participant's DecryptionShares verifier checks its
+// column, one combine_shares_batch over the verdicts, one DiscreteLogSolver::solve over [lo, hi) for all decrypted elements.
+// verifiers[j] = (participant index, its verifier), in the order in which shares are preferred; items[j] = its m packed items.
+// values[c] = nullopt where fewer than `threshold` shares verified or the plaintext is outside the range.
+struct DecryptedTallies {
+  std::vector<std::optional<uint64_t>> values;
+  std::vector<uint8_t> combined;
+  std::vector<uint64_t> used;
+};
+inline DecryptedTallies decrypt_tallies(const Context& ctx, uint64_t shares, uint64_t threshold, const Bytes& ciphertexts,
+                                        const std::vector<std::pair<uint64_t, const ProofParams*>>& verifiers, const std::vector<Bytes>& items,
+                                        const DiscreteLogSolver& solver, uint64_t lo, uint64_t hi) {
+  if (verifiers.size() != items.size()) throw Error(EG_ERR_BAD_ARG, "one column of items per verifier");
+  std::vector<uint64_t> indexes;
+  std::vector<uint32_t> status;
+  Bytes all;
+  for (size_t j = 0; j < verifiers.size(); ++j) {
+    const std::vector<uint32_t> st = verifiers[j].second->verify_batch(items[j]);
+    indexes.push_back(verifiers[j].first);
+    status.insert(status.end(), st.begin(), st.end());
+    all.insert(all.end(), items[j].begin(), items[j].end());
+  }
+  CombinedShares cs = combine_shares_batch(ctx, shares, threshold, ciphertexts, indexes, all, status);
+  DecryptedTallies r;
+  r.values = solver.solve(cs.plain, lo, hi);
+  for (size_t c = 0; c < r.values.size(); ++c) if (!cs.combined[c]) r.values[c] = std::nullopt;
+  r.combined = std::move(cs.combined);
+  r.used = std::move(cs.used);
+  return r;
+}
 
 }  // namespace elastic_elgamal_hip
