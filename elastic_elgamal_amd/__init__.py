@@ -35,7 +35,7 @@ STATUS_NAMES = {
     0: "Ok", 1: "BadScalar", 2: "BadPoint", 3: "OptionsLenMismatch", 4: "Sum(ChallengeMismatch)",
     5: "Range(LenMismatch)", 6: "Range(ChallengeMismatch)", 7: "Variant(LenMismatch)", 8: "Variant(ChallengeMismatch)",
     9: "CreditRange(LenMismatch)", 10: "CreditRange(ChallengeMismatch)", 11: "CreditEquivalence(LenMismatch)",
-    12: "CreditEquivalence(ChallengeMismatch)", 13: "Malformed",
+    12: "CreditEquivalence(ChallengeMismatch)", 13: "Malformed", 14: "Duplicate",
 }
 
 
@@ -196,6 +196,12 @@ def _load() -> C.CDLL:
         "eg_qv_tally_weighted_scratch_bytes": (sz, [vp, sz, C.c_uint32]),
         "eg_qv_tally_weighted_device": (C.c_int, [vp, sz, vp, vp, vp, C.c_int, vp, C.c_uint32, vp, vp, vp, vp, vp, vp]),
         "eg_qv_tally_weighted": (C.c_int, [vp, sz, vp, vp, vp, C.c_int, vp, C.c_uint32, vp, vp, vp]),
+        "eg_choice_weed_scratch_bytes": (sz, [vp, sz, sz]),
+        "eg_choice_weed_device": (C.c_int, [vp, sz, vp, vp, sz, vp, sz, C.c_uint64, vp, vp, vp, vp, vp, vp]),
+        "eg_choice_weed": (C.c_int, [vp, sz, vp, vp, sz, vp, vp, vp, vp, C.POINTER(sz)]),
+        "eg_qv_weed_scratch_bytes": (sz, [vp, sz, sz]),
+        "eg_qv_weed_device": (C.c_int, [vp, sz, vp, vp, sz, vp, sz, C.c_uint64, vp, vp, vp, vp, vp, vp]),
+        "eg_qv_weed": (C.c_int, [vp, sz, vp, vp, sz, vp, vp, vp, vp, C.POINTER(sz)]),
         "eg_proof_params_create": (C.c_int, [vp, cp, C.c_int, C.c_uint64, C.POINTER(vp)]),
         "eg_share_params_create": (C.c_int, [vp, cp, C.c_uint64, C.c_uint64, C.c_uint64, cp, C.POINTER(vp)]),
         "eg_proof_params_destroy": (None, [vp]),
@@ -261,6 +267,10 @@ ABI_VERSION = 7          # include/eg_hip.h: EG_ABI_VERSION
 SMALL_BATCH_MAX = 4096   # include/eg_hip.h: EG_SMALL_BATCH_MAX, the most ballots one verify_small call takes
 GROUP_NONE = 0xFFFFFFFF          # include/eg_hip.h: EG_GROUP_NONE, the group id that leaves a ballot out of every group
 TALLY_GROUPS_MAX = 1 << 24       # include/eg_hip.h: EG_TALLY_GROUPS_MAX
+ST_DUPLICATE = 14                # include/eg_hip.h: EG_ST_DUPLICATE, what weed() writes into status_out for a flagged ballot
+DUP_NONE = 0xFFFFFFFF            # include/eg_hip.h: EG_DUP_NONE
+DUP_PRIOR = 0xFFFFFFFE           # include/eg_hip.h: EG_DUP_PRIOR, a ballot that repeats a ciphertext of the board
+WEED_KEYS_MAX = 1 << 30          # include/eg_hip.h: EG_WEED_KEYS_MAX
 
 
 def pack_json(text, n_options: int, single: bool | None = None, credits: int | None = None, threads: int = 0, max_objects: int = 0):
@@ -929,6 +939,47 @@ class _BatchParams:
         _check(self._fn("tally_weighted_device")(self._h, n, d_ballots or None, d_status or None, d_weights or None, weight_bits,
                                                   d_groups or None, n_groups, d_scratch or None, d_tallies or None, d_weight_sums or None,
                                                   d_counts or None, d_bad or None, stream or None))
+
+    def weed_scratch_bytes(self, n: int, n_prior: int = 0) -> int:
+        """Device scratch that weed_device needs for n ballots beside a board of n_prior ciphertexts (0 for arguments it refuses)."""
+        return int(self._fn("weed_scratch_bytes")(self._h, n, n_prior))
+
+    def weed(self, ballots: bytes, status=None, board: bytes = b"", append: bool = False):
+        """Ballot weeding between verify and tally (eg_*_weed): flags every participating ballot (status word 0; `status` None: every
+        ballot) that repeats a tally ciphertext - 64 wire bytes R || B - of `board` (ciphertexts cast in earlier batches, 64 bytes each)
+        or of an earlier participating ballot of the batch.  Returns (dup_of, status_out, appended): dup_of[b] = DUP_NONE, DUP_PRIOR or
+        the smallest earlier ballot that shares a ciphertext with b (it counts even if it is flagged itself); status_out = the status
+        words with ST_DUPLICATE for the flagged ballots, ready for tally_grouped / tally_weighted; appended = with `append`, the
+        ciphertexts of the participating, unflagged ballots in ballot and option order - what to add to the board - else None."""
+        n = len(ballots) // self.ballot_size
+        if n * self.ballot_size != len(ballots):
+            raise ValueError("ballots is not a whole number of packed ballots")
+        if len(board) % 64:
+            raise ValueError("board is not a whole number of 64-byte ciphertexts")
+        st = None
+        if status is not None:
+            status = list(status)
+            if len(status) != n:
+                raise ValueError("status needs one word per ballot")
+            st = (C.c_uint32 * max(n, 1))(*status)
+        buf = (C.c_char * max(len(ballots), 1)).from_buffer_copy(ballots or b"\0")
+        brd = (C.c_char * max(len(board), 1)).from_buffer_copy(board or b"\0")
+        dup, out = (C.c_uint32 * max(n, 1))(), (C.c_uint32 * max(n, 1))()
+        app = C.create_string_buffer(max(n * self.n_options * 64, 1)) if append else None
+        n_app = sz_t(0)
+        _check(self._fn("weed")(self._h, n, buf, st, len(board) // 64, brd, dup, out, app, C.byref(n_app)))
+        return list(dup[:n]), list(out[:n]), (app.raw[: 64 * n_app.value] if append else None)
+
+    def weed_device(self, n: int, d_ballots: int, d_status: int, n_prior: int, d_board: int, board_cap: int, hash_seed: int, d_scratch: int,
+                    d_dup_of: int, d_found: int, d_status_out: int = 0, d_board_count: int = 0, stream: int = 0):
+        """Asynchronous device-pointer variant (eg_*_weed_device): no allocation, no host synchronisation, no lock.  d_status may be 0
+        (every ballot participates); d_board: board_cap x 64 bytes of which the first n_prior are the board; hash_seed: 64 random bits,
+        fresh per call and unpublished until it is over; d_scratch: weed_scratch_bytes(n, n_prior) bytes; d_dup_of: n uint32;
+        d_status_out may be 0 or d_status; d_board_count: one uint64, 0 = do not append; d_found: three uint32 the library writes
+        (flagged against the board, flagged against the batch, the bad word - discard the results if it is non-zero)."""
+        _check(self._fn("weed_device")(self._h, n, d_ballots or None, d_status or None, n_prior, d_board or None, board_cap,
+                                        hash_seed & 0xFFFFFFFFFFFFFFFF, d_scratch or None, d_dup_of or None, d_status_out or None,
+                                        d_board_count or None, d_found or None, stream or None))
 
 
 class ChoiceParams(_BatchParams):

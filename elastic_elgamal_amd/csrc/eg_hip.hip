@@ -15,6 +15,7 @@
 #include <functional>
 #include <memory>
 #include <mutex>
+#include <random>
 #include <string>
 #include <thread>
 #include <condition_variable>
@@ -32,6 +33,7 @@
 #include "dlog_kernels.cuh"
 #include "group_tally_kernels.cuh"
 #include "share_combine_kernels.cuh"
+#include "weed_kernels.cuh"
 
 using namespace eg;
 
@@ -259,6 +261,7 @@ struct Engine {
   egplan::StatusRule* d_rules = nullptr;
   u32* d_tally_slots = nullptr;
   u32* d_tally_items = nullptr;                // wire item behind every tally slot (group_tally_host.hpp: tally_items): what the per-group tally reads
+  bool weed_keys_ok = false;                   // the B item of every tally ciphertext is its R item + 1 (weed_host.hpp: key_items), checked at creation
   unsigned short* d_base_slots = nullptr;      // FlatPlan::build_slots: point slots by the stage that builds their tables
   egplan::SumBase* d_sum_bases = nullptr;      // FlatPlan::sums / sum_members (members as table slots)
   unsigned short* d_sum_members = nullptr;
@@ -511,6 +514,8 @@ static int engine_create(eg_ctx* ctx, eghost::Plan&& plan, const uint8_t pk[32],
     const std::vector<uint32_t> items = eggt::tally_items(P.pt_items, P.tally_slots);
     for (uint32_t it : items) if (it == 0xffffffffu) return fail(EG_ERR_BAD_ARG, "internal: a tally slot of the plan is not a wire point");
     if ((rc = upload(&e->d_tally_items, items, s))) return rc;
+    std::vector<uint32_t> r_items;
+    e->weed_keys_ok = egw::key_items(r_items, items) && P.stride % 16 == 0;
   }
   if ((rc = upload(&e->d_base_slots, F.build_slots, s))) return rc;
   if ((rc = upload(&e->d_sum_bases, F.sums, s))) return rc;
@@ -2302,6 +2307,143 @@ int eg_choice_tally_weighted(eg_choice_params* p, size_t n, const uint8_t* ballo
 int eg_qv_tally_weighted(eg_qv_params* p, size_t n, const uint8_t* ballots, const uint32_t* status, const uint64_t* weights, int weight_bits,
                          const uint32_t* groups, uint32_t n_groups, uint8_t* tallies, uint64_t* weight_sums, uint32_t* counts) {
   return weighted_host(p ? p->eng : nullptr, n, ballots, status, weights, weight_bits, groups, n_groups, tallies, weight_sums, counts);
+}
+// ---- ballot weeding: accepted ballots that repeat a tally ciphertext of the board or of an earlier ballot (weed_kernels.cuh) ----------------
+// Stateless like the grouped pass: the plan's immutable data only (stride, tally items, the adjacency checked at creation).
+static uint32_t weed_keys_per_ballot(const Engine* e) { return (uint32_t)(e->plan.tally_slots.size() / 2); }
+static size_t weed_scratch_bytes(const Engine* e, size_t n, size_t n_prior) {
+  if (!e || !e->weed_keys_ok || egw::refuse(n, n_prior, n_prior) || egw::refuse_keys(n, n_prior, weed_keys_per_ballot(e))) return 0;
+  return egw::layout(n, n_prior, weed_keys_per_ballot(e)).total;
+}
+// what both forms refuse before they look at the params object; `append`: the caller asked for the board to be extended
+static int weed_check(const Engine* e, size_t n, size_t n_prior, size_t board_cap, bool have_ballots, bool have_dup_of, bool have_found,
+                      bool have_board, bool append) {
+  const char* why = egw::refuse(n, n_prior, board_cap);
+  if (!why && n && !have_ballots) why = "null ballots";
+  if (!why && n && !have_dup_of) why = "null dup_of";
+  if (!why && n && !have_found) why = "null found";
+  if (!why && !have_board && n_prior) why = "null board with n_prior > 0";
+  if (!why && !have_board && append) why = "null board with an append requested";
+  if (why) return fail(EG_ERR_BAD_ARG, std::string("weed: ") + why);
+  if (!e) return fail(EG_ERR_BAD_ARG, "weed: null params");
+  if (!e->weed_keys_ok) return fail(EG_ERR_BAD_ARG, "weed: internal: the tally ciphertexts of this plan are not contiguous wire items");
+  if ((why = egw::refuse_keys(n, n_prior, weed_keys_per_ballot(e)))) return fail(EG_ERR_BAD_ARG, std::string("weed: ") + why);
+  return EG_OK;
+}
+static int weed_launch(Engine* e, size_t n, const void* d_ballots, const void* d_status, size_t n_prior, void* d_board, size_t board_cap,
+                       uint64_t hash_seed, void* d_scratch, void* d_dup_of, void* d_status_out, void* d_board_count, void* d_found, hipStream_t s) {
+  if (((uintptr_t)d_ballots | (uintptr_t)d_board | (uintptr_t)d_scratch) & 15u)
+    return fail(EG_ERR_BAD_ARG, "weed: ballots, board and scratch must be 16-byte aligned");
+  if (((uintptr_t)d_status | (uintptr_t)d_dup_of | (uintptr_t)d_status_out | (uintptr_t)d_found) & 3u || ((uintptr_t)d_board_count & 7u))
+    return fail(EG_ERR_BAD_ARG, "weed: misaligned device pointer");
+  TRY_(weed_check(e, n, n_prior, board_cap, d_ballots != nullptr, d_dup_of != nullptr, d_found != nullptr, d_board != nullptr,
+                  d_board_count != nullptr));
+  const u32 K = weed_keys_per_ballot(e);
+  const egw::Layout L = egw::layout(n, n_prior, K);
+  if (L.total && !d_scratch) return fail(EG_ERR_BAD_ARG, "weed: null scratch (eg_*_weed_scratch_bytes says how much)");
+  if (!d_found && !d_board_count) return EG_OK;                          // n == 0 and nowhere to write anything to
+  HIPCHK(hipSetDevice(e->ctx->device));
+  char* base = static_cast<char*>(d_scratch);
+  u32* found = static_cast<u32*>(d_found);
+  const u32* status = static_cast<const u32*>(d_status);
+  const WeedKeysDev keys{static_cast<const uint8_t*>(d_ballots), static_cast<const uint8_t*>(d_board), (const u32*)e->d_tally_items,
+                         (uint64_t)e->plan.stride, (uint64_t)n, (uint64_t)n_prior, K};
+  const int cap = e->ctx->cus * 64;
+  if (found) HIPCHK(hipMemsetAsync(found, 0, 3 * sizeof(u32), s));       // (n == 0 may come without: n_prior <= board_cap always fits)
+  if (n) {
+    unsigned long long* slots = reinterpret_cast<unsigned long long*>(base + L.table);
+    u32* pos = reinterpret_cast<u32*>(base + L.pos);
+    HIPCHK(hipMemsetAsync(slots, 0xff, (size_t)L.slots * sizeof(uint64_t), s));          // egw::EMPTY
+    hipLaunchKernelGGL(k_weed_insert, dim3(grid_for(n_prior + n * K, cap)), dim3(WEED_NT), 0, s, keys, status, slots, L.slots, hash_seed, found);
+    hipLaunchKernelGGL(k_weed_lookup, dim3(blocks_of(n)), dim3(WEED_NT), 0, s, keys, status, (const unsigned long long*)slots, L.slots, hash_seed,
+                       static_cast<u32*>(d_dup_of), static_cast<u32*>(d_status_out), pos, found);
+    if (d_board_count) {
+      u32* tiles = reinterpret_cast<u32*>(base + L.tiles);
+      u32* total_word = reinterpret_cast<u32*>(base + L.total_word);
+      hipLaunchKernelGGL(k_weed_scan_tiles, dim3(L.n_tiles), dim3(WEED_NT), 0, s, (const u32*)pos, (u32)n, tiles);
+      hipLaunchKernelGGL(k_weed_scan_tops, dim3(1), dim3(64), 0, s, L.n_tiles, tiles, K, (uint64_t)n_prior, (uint64_t)board_cap, total_word,
+                         static_cast<unsigned long long*>(d_board_count), found);
+      hipLaunchKernelGGL(k_weed_scan_apply, dim3(L.n_tiles), dim3(WEED_NT), 0, s, pos, (u32)n, (const u32*)tiles);
+      hipLaunchKernelGGL(k_weed_copy, dim3(grid_for(n * K * 4, cap)), dim3(WEED_NT), 0, s, keys, (const u32*)pos, (const u32*)total_word,
+                         static_cast<uint8_t*>(d_board), (uint64_t)board_cap);
+    }
+  } else if (d_board_count) {                                             // nothing to add: the count is n_prior
+    hipLaunchKernelGGL(k_weed_scan_tops, dim3(1), dim3(64), 0, s, 0u, (u32*)nullptr, K, (uint64_t)n_prior, (uint64_t)board_cap, (u32*)nullptr,
+                       static_cast<unsigned long long*>(d_board_count), found);
+  }
+  HIPCHK(hipGetLastError());
+  return EG_OK;
+}
+static uint64_t weed_draw_seed() {
+  std::random_device rd;
+  return ((uint64_t)rd() << 32) ^ (uint64_t)rd();
+}
+// host buffers, staged as grouped_host stages them; the board is staged with room for every key of the batch when `appended` is given
+static int weed_host(Engine* e, size_t n, const uint8_t* ballots, const uint32_t* status, size_t n_prior, const uint8_t* board, uint32_t* dup_of,
+                     uint32_t* status_out, uint8_t* appended, size_t* n_appended) {
+  if (n_appended) *n_appended = 0;
+  TRY_(weed_check(e, n, n_prior, n_prior, ballots != nullptr, dup_of != nullptr, true, board != nullptr, false));
+  if (appended && !n_appended) return fail(EG_ERR_BAD_ARG, "weed: null n_appended");
+  HIPCHK(hipSetDevice(e->ctx->device));
+  const size_t K = weed_keys_per_ballot(e), stride = e->plan.stride;
+  const size_t board_cap = n_prior + (appended ? n * K : 0);
+  enum { BALLOTS, STATUS, BOARD, SCRATCH, DUP, OUT, N_BUF };
+  const size_t sizes[N_BUF] = {n * stride, status ? n * 4 : 0, board_cap * egw::KEY_BYTES, weed_scratch_bytes(e, n, n_prior), n * 4,
+                               n * 4 + 32};          // OUT: status_out, then (8-byte aligned) the board count and the three counters
+  void* d[N_BUF] = {};
+  hipStream_t s = nullptr;
+  ScopeExit release{[&]() {
+    for (void* p : d) if (p) (void)hipFree(p);
+    if (s) (void)hipStreamDestroy(s);
+  }};
+  for (int k = 0; k < N_BUF; ++k) {
+    const hipError_t he = hipMalloc(&d[k], std::max<size_t>(sizes[k], 16));
+    if (he == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(EG_ERR_NOMEM, "weed: the staging buffers do not fit the device memory"); }
+    HIPCHK(he);
+  }
+  HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+  if (n) HIPCHK(hipMemcpyAsync(d[BALLOTS], ballots, sizes[BALLOTS], hipMemcpyHostToDevice, s));
+  if (n && status) HIPCHK(hipMemcpyAsync(d[STATUS], status, sizes[STATUS], hipMemcpyHostToDevice, s));
+  if (n_prior) HIPCHK(hipMemcpyAsync(d[BOARD], board, n_prior * egw::KEY_BYTES, hipMemcpyHostToDevice, s));
+  char* tail = static_cast<char*>(d[OUT]) + (n * 4 + 7) / 8 * 8;
+  unsigned long long* d_count = reinterpret_cast<unsigned long long*>(tail);
+  u32* d_found = reinterpret_cast<u32*>(tail + 8);
+  TRY_(weed_launch(e, n, d[BALLOTS], status ? d[STATUS] : nullptr, n_prior, d[BOARD], board_cap, weed_draw_seed(), d[SCRATCH], d[DUP],
+                   status_out ? d[OUT] : nullptr, appended ? d_count : nullptr, d_found, s));
+  u32 found[3] = {0, 0, 0};
+  unsigned long long count = n_prior;
+  if (n) HIPCHK(hipMemcpyAsync(dup_of, d[DUP], n * 4, hipMemcpyDeviceToHost, s));
+  if (n && status_out) HIPCHK(hipMemcpyAsync(status_out, d[OUT], n * 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(found, d_found, sizeof found, hipMemcpyDeviceToHost, s));
+  if (appended) HIPCHK(hipMemcpyAsync(&count, d_count, sizeof count, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  if (appended && count > n_prior && count <= board_cap) {
+    HIPCHK(hipMemcpyAsync(appended, static_cast<char*>(d[BOARD]) + n_prior * egw::KEY_BYTES, (count - n_prior) * egw::KEY_BYTES, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    *n_appended = (size_t)(count - n_prior);
+  }
+  if (found[2]) return fail(EG_ERR_BAD_ARG, "weed: the table overflowed or the board has no room (" + std::to_string(found[2]) + "): discard the results");
+  return EG_OK;
+}
+size_t eg_choice_weed_scratch_bytes(const eg_choice_params* p, size_t n, size_t n_prior) { return weed_scratch_bytes(p ? p->eng : nullptr, n, n_prior); }
+size_t eg_qv_weed_scratch_bytes(const eg_qv_params* p, size_t n, size_t n_prior) { return weed_scratch_bytes(p ? p->eng : nullptr, n, n_prior); }
+int eg_choice_weed_device(eg_choice_params* p, size_t n, const void* d_ballots, const void* d_status, size_t n_prior, void* d_board, size_t board_cap,
+                          uint64_t hash_seed, void* d_scratch, void* d_dup_of, void* d_status_out, void* d_board_count, void* d_found, void* stream) {
+  return weed_launch(p ? p->eng : nullptr, n, d_ballots, d_status, n_prior, d_board, board_cap, hash_seed, d_scratch, d_dup_of, d_status_out,
+                     d_board_count, d_found, (hipStream_t)stream);
+}
+int eg_qv_weed_device(eg_qv_params* p, size_t n, const void* d_ballots, const void* d_status, size_t n_prior, void* d_board, size_t board_cap,
+                      uint64_t hash_seed, void* d_scratch, void* d_dup_of, void* d_status_out, void* d_board_count, void* d_found, void* stream) {
+  return weed_launch(p ? p->eng : nullptr, n, d_ballots, d_status, n_prior, d_board, board_cap, hash_seed, d_scratch, d_dup_of, d_status_out,
+                     d_board_count, d_found, (hipStream_t)stream);
+}
+int eg_choice_weed(eg_choice_params* p, size_t n, const uint8_t* ballots, const uint32_t* status, size_t n_prior, const uint8_t* board,
+                   uint32_t* dup_of, uint32_t* status_out, uint8_t* appended, size_t* n_appended) {
+  return weed_host(p ? p->eng : nullptr, n, ballots, status, n_prior, board, dup_of, status_out, appended, n_appended);
+}
+int eg_qv_weed(eg_qv_params* p, size_t n, const uint8_t* ballots, const uint32_t* status, size_t n_prior, const uint8_t* board, uint32_t* dup_of,
+               uint32_t* status_out, uint8_t* appended, size_t* n_appended) {
+  return weed_host(p ? p->eng : nullptr, n, ballots, status, n_prior, board, dup_of, status_out, appended, n_appended);
 }
 // builds the wide comb tables now (synchronously, ~12 GB each for G and K) instead of inside the first large verify call
 static int prepare_wide(Engine* e) {

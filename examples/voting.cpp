@@ -1,7 +1,7 @@
 // voting.cpp -- the reference's examples/voting.rs on the GPU backend, in C++ on top of the C ABI:
 //   `Args::vote`            (examples/voting.rs:179-213)  ./voting [votes] [options] [seed]
 //   `Args::quadratic_vote`  (examples/voting.rs:219-269)  ./voting --qv [votes] [options] [credits] [seed]
-//   options: --devices N, --json, --precincts P, --weighted
+//   options: --devices N, --json, --precincts P, --weighted, --replays K
 // talliers' key -> voters create ballots from their own choices -> verify every ballot -> homomorphic totals -> decrypt and
 // compare with the EXPECTED totals the voters' choices add up to.  Threshold sharing of the key (examples/voting.rs:105-120) is out
 // of scope; a single key pair stands in for the shared key (tests/test_gpu_parity.py::test_threshold_tally_end_to_end
@@ -14,6 +14,9 @@
 // With --weighted voter v also holds a weight (shares, stake): 1 + 7919 v mod 65535.  The weighted totals of the same verified batch
 // (tally_weighted = eg_*_tally_weighted: total += ciphertext * weight, the reference's impl Mul<u64> for Ciphertext) are decrypted and read
 // with the discrete-log solver over [0, sum of the counted weights x most votes per option] - the table above would not reach that far.
+// With --replays K, K extra voters resubmit byte-for-byte copies of earlier ballots.  The reference's proofs bind nothing of the voter, so
+// every copy of an accepted ballot verifies; the flow weeds between verify and tally (weed = eg_*_weed: ballots that repeat a ciphertext
+// are flagged), prints the number dropped, tallies what is left (tally_grouped over the weeded status words) and reaches the same totals.
 //
 //   g++ -std=c++17 -Iinclude examples/voting.cpp -Lelastic_elgamal_amd -leg_hip -Wl,-rpath,$PWD/elastic_elgamal_amd -o voting
 #include <cstdio>
@@ -115,6 +118,33 @@ static bool weighted_tally(const Context& ctx, const Ristretto& group, const Sca
   return ok;
 }
 
+// --replays: K extra voters resubmit copies of earlier ballots; verify, weed, tally what is left - the totals of the honest voters
+template <class Params>
+static bool replayed_tally(const Context& ctx, const Ristretto& group, const Scalar& sk, const Params& params, const Bytes& ballots, size_t votes,
+                           size_t replays, const std::vector<uint64_t>& expected, uint64_t max_value) {
+  const size_t size = params.ballot_size();
+  Bytes all = ballots;
+  for (size_t i = 0; i < replays; ++i) {
+    const size_t from = (7 * i + 1) % votes;
+    all.insert(all.end(), ballots.begin() + from * size, ballots.begin() + (from + 1) * size);
+  }
+  const auto verdict = params.verify_batch(all);
+  printf("with %zu replayed ballots: %zu of %zu ballots verified\n", replays, verdict.accepted(), votes + replays);
+  std::vector<uint32_t> status(votes + replays);
+  size_t copies_accepted = 0;
+  for (size_t v = 0; v < votes + replays; ++v) { status[v] = verdict.results[v] ? 1u : 0u; copies_accepted += v >= votes && !status[v]; }
+  const Weeded w = params.weed(all, status);
+  for (size_t v = 0; v < w.dup_of.size(); ++v)
+    if (w.dup_of[v] != EG_DUP_NONE) printf("  voter #%zu dropped: repeats a ciphertext of voter #%u\n", v + 1, w.dup_of[v] + 1);
+  printf("weeding dropped %zu ballots\n", w.dropped());
+  const GroupedTally kept = params.tally_grouped(all, w.status, std::vector<uint32_t>(votes + replays, 0u), 1);
+  bool ok = w.dropped() == copies_accepted && kept.accepted[0] == verdict.accepted() - copies_accepted;
+  for (size_t v = 0; v < votes; ++v) ok = ok && w.dup_of[v] == EG_DUP_NONE;
+  ok = tally(ctx, group, sk, kept.totals[0], expected, max_value) && ok;
+  printf("the weeded totals %s those without the replays\n", ok ? "equal" : "DIFFER from");
+  return ok;
+}
+
 // serde's human-readable form of an EncryptedChoice (src/serde.rs:19-80: every element and scalar as unpadded base64url; field names of
 // choice.rs:276-280, ring.rs:282-287, log_equality.rs:96-101), from the packed ballot
 static std::string b64url(const uint8_t* p, size_t n) {
@@ -142,7 +172,7 @@ static std::string choice_to_json(const uint8_t* b, size_t options) {
 int main(int argc, char** argv) {
   bool qv = false, json = false, weighted = false;
   int devices = 1;
-  long precincts = 0;
+  long precincts = 0, replays = 0;
   std::vector<std::string> pos;
   for (int i = 1; i < argc; ++i) {
     if (!strcmp(argv[i], "--qv")) qv = true;
@@ -150,12 +180,14 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "--weighted")) weighted = true;
     else if (!strcmp(argv[i], "--devices") && i + 1 < argc) devices = atoi(argv[++i]);
     else if (!strcmp(argv[i], "--precincts") && i + 1 < argc) precincts = atol(argv[++i]);
+    else if (!strcmp(argv[i], "--replays") && i + 1 < argc) replays = atol(argv[++i]);
     else pos.push_back(argv[i]);
   }
   auto arg = [&](size_t k, uint64_t dflt) { return k < pos.size() ? strtoull(pos[k].c_str(), nullptr, 10) : dflt; };
   const size_t votes = (size_t)arg(0, 1000), options = (size_t)arg(1, 5);
   const uint64_t credits = qv ? arg(2, 20) : 0, seed = arg(qv ? 3 : 2, 1);
   if (devices < 1 || devices > 16) { printf("--devices must be in 1..16\n"); return 2; }
+  if (replays < 0 || replays > 1000000 || (replays && !votes)) { printf("--replays must be in 0..1000000 and needs a voter to copy\n"); return 2; }
   if (precincts < 0 || precincts > (long)EG_TALLY_GROUPS_MAX) { printf("--precincts must be in 0..%u\n", EG_TALLY_GROUPS_MAX); return 2; }
 
   // one context per device slot; slot d uses GPU d when the process sees that many, else GPU 0
@@ -218,6 +250,7 @@ int main(int argc, char** argv) {
       for (size_t i = 0; i < votes; ++i) one_hot[i * options + choices[i]] = 1u;
       ok = weighted_tally(ctx, group, sk, *params[0], ballots, verdict, one_hot, options, 1) && ok;
     }
+    if (replays) ok = replayed_tally(ctx, group, sk, *params[0], ballots, votes, (size_t)replays, expected, votes) && ok;
   } else {
     std::vector<std::unique_ptr<QuadraticVotingParams>> params;
     for (auto& c : ctxs) params.push_back(std::make_unique<QuadraticVotingParams>(*c, pk, options, credits));
@@ -249,6 +282,7 @@ int main(int argc, char** argv) {
     ok = verdict.accepted() == votes - (forged < votes ? 1 : 0) && tally(ctx, group, sk, verdict.totals, expected, max_votes);
     if (precincts) ok = precinct_tally(ctx, group, sk, *params[0], ballots, verdict, (uint32_t)precincts, expected_by_precinct, expected, max_votes) && ok;
     if (weighted) ok = weighted_tally(ctx, group, sk, *params[0], ballots, verdict, all, options, params[0]->max_votes()) && ok;
+    if (replays) ok = replayed_tally(ctx, group, sk, *params[0], ballots, votes, (size_t)replays, expected, max_votes) && ok;
   }
   printf("%s: the decrypted totals %s the expected ones\n", ok ? "OK" : "MISMATCH", ok ? "equal" : "differ from");
   return ok ? 0 : 1;

@@ -109,8 +109,10 @@ enum {
   EG_ST_QV_CREDIT_RANGE_CHALLENGE = 10, /* QuadraticVotingError::CreditRange (quadratic_voting.rs:341) */
   EG_ST_QV_CREDIT_EQUIV_LEN = 11,
   EG_ST_QV_CREDIT_EQUIV_CHALLENGE = 12, /* QuadraticVotingError::CreditEquivalence (:343) */
-  EG_ST_MALFORMED = 13            /* the ballot object does not deserialise at all (bad base64url / byte length, fewer than 2
+  EG_ST_MALFORMED = 13,           /* the ballot object does not deserialise at all (bad base64url / byte length, fewer than 2
                                      responses, wrong proof kind: serde.rs:29-80,303-355); object-ingest layer only */
+  EG_ST_DUPLICATE = 14            /* no verdict of the reference: an accepted ballot that repeats a tally ciphertext of the board or of an
+                                     earlier ballot; written by eg_*_weed* into status_out only, detail 0 */
 };
 #define EG_STATUS_KIND(s) ((s) & 0xffu)
 #define EG_STATUS_DETAIL(s) ((s) >> 8)
@@ -430,6 +432,59 @@ int eg_qv_tally_weighted_device(eg_qv_params*, size_t n, const void* d_ballots, 
 int eg_qv_tally_weighted(eg_qv_params*, size_t n, const uint8_t* ballots, const uint32_t* status, const uint64_t* weights,
                          int weight_bits, const uint32_t* groups /* may be NULL */, uint32_t n_groups, uint8_t* tallies,
                          uint64_t* weight_sums /* may be NULL */, uint32_t* counts /* may be NULL */);
+
+/* ---- ballot weeding: accepted ballots that repeat a ciphertext of the bulletin board or of an earlier ballot, flagged in one pass --------
+ * The reference's transcripts start from fixed labels and bind the key and the ciphertexts (src/app/choice.rs:72,323,376), nothing of
+ * the voter: a byte-for-byte copy of somebody's ballot verifies and would be tallied, and the change in the result reveals the copied
+ * vote (Cortier and Smyth, "Attacking and fixing Helios").  These entries run between a verify entry and a tally entry, over the same
+ * packed ballots, and say which ballots to drop.
+ * KEYS.  A ballot's keys are its tally ciphertexts, the 64 wire bytes R || B behind each pair of tally slots: n_options of them (for
+ * quadratic voting the vote ciphertexts; partial ciphertexts and the credit ciphertext are not keys).  Equality is byte equality - accepted
+ * ballots have canonical encodings - and nothing is decoded.  Ballot b PARTICIPATES iff status[b] == EG_ST_OK (d_status NULL: every
+ * ballot); bytes of other ballots are never read.  The BOARD is the caller's compact array of ciphertexts cast in earlier batches:
+ * n_prior x 64 bytes in a buffer with room for board_cap.
+ * THE RULE.  dup_of[b] = EG_DUP_NONE for a ballot that does not participate or shares no key; EG_DUP_PRIOR if any key of b is on the
+ * board; otherwise the smallest index b' < b of a participating ballot that shares at least one key with b, at any option position.
+ * The rule is NOT sequential: b' counts even if b' is itself flagged - A{x,y}, B{y,z}, C{z,w} flags B (0) and C (1) - so the verdict is a
+ * pure function of the inputs that depends neither on hash_seed nor on the order in which lanes run.  Honest ballots never share a
+ * ciphertext, so only adversarial ballots can tell this from the sequential rule.  The same key twice inside one ballot is no duplicate.
+ * status_out (optional, may be d_status itself) = status[b], or EG_ST_DUPLICATE for a flagged ballot: the words to hand to
+ * eg_*_tally_grouped / _weighted.  The library WRITES found[0] = ballots flagged against the board, found[1] = ballots flagged against
+ * the batch, found[2] = the bad word: non-zero if the table overflowed (it cannot with the library's own sizing; the probe loop is
+ * bounded and reports instead of spinning) or if the append below did not fit - discard the results then.
+ * APPEND (d_board_count != NULL).  The keys of every participating, unflagged ballot are written behind the first n_prior entries, in
+ * ballot order and then option order, and *d_board_count (uint64) = n_prior + appended.  If they do not fit board_cap nothing is
+ * appended, the count is n_prior and found[2] is set.
+ * hash_seed: 64 bits the caller draws at random per call and does not publish before the call is over (the host form draws its own).
+ * The ballots are untrusted: under a public hash, valid ballots with keys on one probe chain would make the pass quadratic.
+ *
+ * STATELESS as the grouped pass: the params object's immutable plan only - no lock, no workspace, no running tally.  The `_device` form
+ * is asynchronous on `stream`, allocates nothing and never synchronises; d_scratch holds eg_*_weed_scratch_bytes(params, n, n_prior)
+ * bytes (0 for arguments that would be refused, and for n == 0): 8 bytes per slot of a table of the smallest power of two >= 2 (n
+ * n_options + n_prior), at least 1024, and ~4 bytes per ballot.  The host form returns EG_ERR_BAD_ARG AFTER writing its outputs when
+ * found[2] != 0; appended (optional, room for n x n_options x 64 bytes) receives the appended keys and *n_appended their number.
+ * EG_ERR_BAD_ARG before anything is launched: n >= 2^31, n_prior >= 2^31, n n_options + n_prior above EG_WEED_KEYS_MAX, n_prior >
+ * board_cap, a NULL d_ballots / d_dup_of / d_found with n > 0, a NULL d_board with n_prior > 0 or with an append requested, a NULL
+ * scratch pointer when the size is not 0, ballots, board or scratch that are not 16-byte aligned.  n == 0 is valid. */
+#define EG_DUP_NONE 0xffffffffu
+#define EG_DUP_PRIOR 0xfffffffeu
+#define EG_WEED_KEYS_MAX (1u << 30) /* n * keys_per_ballot + n_prior */
+size_t eg_choice_weed_scratch_bytes(const eg_choice_params*, size_t n, size_t n_prior);
+int eg_choice_weed_device(eg_choice_params*, size_t n, const void* d_ballots, const void* d_status /* or NULL */, size_t n_prior,
+                          void* d_board /* board_cap x 64 */, size_t board_cap, uint64_t hash_seed, void* d_scratch,
+                          void* d_dup_of /* n x uint32 */, void* d_status_out /* or NULL */,
+                          void* d_board_count /* uint64, or NULL: no append */, void* d_found /* 3 x uint32 */, void* stream);
+int eg_choice_weed(eg_choice_params*, size_t n, const uint8_t* ballots, const uint32_t* status /* or NULL */, size_t n_prior,
+                   const uint8_t* board, uint32_t* dup_of, uint32_t* status_out /* or NULL */,
+                   uint8_t* appended /* or NULL; room for n * n_options * 64 */, size_t* n_appended);
+size_t eg_qv_weed_scratch_bytes(const eg_qv_params*, size_t n, size_t n_prior);
+int eg_qv_weed_device(eg_qv_params*, size_t n, const void* d_ballots, const void* d_status /* or NULL */, size_t n_prior,
+                      void* d_board /* board_cap x 64 */, size_t board_cap, uint64_t hash_seed, void* d_scratch,
+                      void* d_dup_of /* n x uint32 */, void* d_status_out /* or NULL */,
+                      void* d_board_count /* uint64, or NULL: no append */, void* d_found /* 3 x uint32 */, void* stream);
+int eg_qv_weed(eg_qv_params*, size_t n, const uint8_t* ballots, const uint32_t* status /* or NULL */, size_t n_prior,
+               const uint8_t* board, uint32_t* dup_of, uint32_t* status_out /* or NULL */,
+               uint8_t* appended /* or NULL; room for n * n_options * 64 */, size_t* n_appended);
 
 /* ---- batch tier on several GPUs of ONE process (SURVEY.md 8b `device_mask`; the reference's host is one single-threaded process,
  * examples/voting.rs:179-213) -----------------------------------------------------------------------------------------------------

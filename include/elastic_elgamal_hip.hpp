@@ -147,6 +147,15 @@ inline WeightedTally unpack_weighted(const Bytes& t, const std::vector<uint64_t>
   return w;
 }
 
+// Ballot weeding (eg_*_weed): dup_of[b] = EG_DUP_NONE, EG_DUP_PRIOR (a ciphertext of b is on the board) or the smallest earlier ballot that
+// shares a ciphertext with b; status = the caller's words with EG_ST_DUPLICATE for the flagged ballots (what a tally entry takes);
+// appended = the ciphertexts of the participating, unflagged ballots in ballot and option order (64 bytes each): what joins the board.
+struct Weeded {
+  std::vector<uint32_t> dup_of, status;
+  Bytes appended;
+  size_t dropped() const { size_t d = 0; for (uint32_t v : dup_of) d += v != EG_DUP_NONE; return d; }
+};
+
 // ChoiceParams<G, S> (choice.rs:132-196); S is SingleChoice (sum proof) or MultiChoice
 class ChoiceParams {
  public:
@@ -228,6 +237,30 @@ class ChoiceParams {
                              void* stream = nullptr) const {
     check(eg_choice_tally_weighted_device(p_, n, d_ballots, d_status, d_weights, weight_bits, d_groups, n_groups, d_scratch, d_tallies,
           d_weight_sums, d_counts, d_bad, stream));
+  }
+  // ballot weeding between verify and tally: `status` = the words a verify entry wrote for `packed` (empty: every ballot participates),
+  // `board` = the ciphertexts cast in earlier batches, 64 bytes each.  Stateless.
+  Weeded weed(const Bytes& packed, const std::vector<uint32_t>& status = {}, const Bytes& board = Bytes(), bool append = true) const {
+    const size_t n = packed.size() / ballot_size();
+    if (n * ballot_size() != packed.size() || (!status.empty() && status.size() != n) || board.size() % 64)
+      throw Error(EG_ERR_BAD_ARG, "packed, status and board do not describe whole ballots and ciphertexts");
+    Weeded w;
+    w.dup_of.resize(n);
+    w.status.resize(n);
+    w.appended.resize(append ? n * n_ * 64 : 0);
+    size_t n_appended = 0;
+    const int rc = eg_choice_weed(p_, n, packed.data(), status.empty() ? nullptr : status.data(), board.size() / 64, board.data(), w.dup_of.data(),
+                   w.status.data(), append ? w.appended.data() : nullptr, &n_appended);
+    w.appended.resize(n_appended * 64);
+    check(rc);
+    return w;
+  }
+  // asynchronous device-pointer form: d_scratch of weed_scratch_bytes(n, n_prior) bytes, d_found three uint32 the library writes
+  size_t weed_scratch_bytes(size_t n, size_t n_prior) const { return eg_choice_weed_scratch_bytes(p_, n, n_prior); }
+  void weed_device(size_t n, const void* d_ballots, const void* d_status, size_t n_prior, void* d_board, size_t board_cap, uint64_t hash_seed,
+                   void* d_scratch, void* d_dup_of, void* d_status_out, void* d_board_count, void* d_found, void* stream = nullptr) const {
+    check(eg_choice_weed_device(p_, n, d_ballots, d_status, n_prior, d_board, board_cap, hash_seed, d_scratch, d_dup_of, d_status_out, d_board_count,
+          d_found, stream));
   }
   // EncryptedChoice::new for synthetic voters base_seed + first + i (choice.rs:313-349), packed
   Bytes encrypt_batch(uint64_t base_seed, size_t first, size_t n, int n_selected = 0) const {
@@ -336,6 +369,30 @@ class QuadraticVotingParams {
                              void* stream = nullptr) const {
     check(eg_qv_tally_weighted_device(p_, n, d_ballots, d_status, d_weights, weight_bits, d_groups, n_groups, d_scratch, d_tallies,
           d_weight_sums, d_counts, d_bad, stream));
+  }
+  // ballot weeding between verify and tally: `status` = the words a verify entry wrote for `packed` (empty: every ballot participates),
+  // `board` = the ciphertexts cast in earlier batches, 64 bytes each.  Stateless.
+  Weeded weed(const Bytes& packed, const std::vector<uint32_t>& status = {}, const Bytes& board = Bytes(), bool append = true) const {
+    const size_t n = packed.size() / ballot_size();
+    if (n * ballot_size() != packed.size() || (!status.empty() && status.size() != n) || board.size() % 64)
+      throw Error(EG_ERR_BAD_ARG, "packed, status and board do not describe whole ballots and ciphertexts");
+    Weeded w;
+    w.dup_of.resize(n);
+    w.status.resize(n);
+    w.appended.resize(append ? n * n_ * 64 : 0);
+    size_t n_appended = 0;
+    const int rc = eg_qv_weed(p_, n, packed.data(), status.empty() ? nullptr : status.data(), board.size() / 64, board.data(), w.dup_of.data(),
+                   w.status.data(), append ? w.appended.data() : nullptr, &n_appended);
+    w.appended.resize(n_appended * 64);
+    check(rc);
+    return w;
+  }
+  // asynchronous device-pointer form: d_scratch of weed_scratch_bytes(n, n_prior) bytes, d_found three uint32 the library writes
+  size_t weed_scratch_bytes(size_t n, size_t n_prior) const { return eg_qv_weed_scratch_bytes(p_, n, n_prior); }
+  void weed_device(size_t n, const void* d_ballots, const void* d_status, size_t n_prior, void* d_board, size_t board_cap, uint64_t hash_seed,
+                   void* d_scratch, void* d_dup_of, void* d_status_out, void* d_board_count, void* d_found, void* stream = nullptr) const {
+    check(eg_qv_weed_device(p_, n, d_ballots, d_status, n_prior, d_board, board_cap, hash_seed, d_scratch, d_dup_of, d_status_out, d_board_count,
+          d_found, stream));
   }
   // QuadraticVotingBallot::new(&params, votes, rng) for voters base_seed + first + i (quadratic_voting.rs:234-284); votes:
   // options_count() numbers per voter with sum(v^2) <= credits.  VARIABLE TIME in the votes (see eg_hip.h): test / synthetic data only.
