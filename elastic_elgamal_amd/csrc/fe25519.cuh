@@ -23,7 +23,8 @@
 //                    0.9766 * 2^64 at 12.5 (0.9785 with the 0.1 % + 4096 that fe_check_values tolerates), 2^64 at 12.8; the final
 //                    carry stays below 2^36.  Pinned by tests/limb_cases.py (column model, corner cases) on the host and on the GPU.
 //   fe_sq(h, f):     needs class(f) <= 3.5 (largest column sum 0.957 * 2^64); output class 1.
-//   fe_add:          class(f) + class(g) <= 7.9.     fe_sub: class(f) + 2 (g must be class 1).
+//   fe_sq2_sub(h, f, g) = 2 f^2 + 4p - g: needs class(f) <= 2.5 (the doubled products: 2 class(f)^2 <= 12.5) and g < class 4; class 1.
+//   fe_add:          class(f) + class(g) <= 7.9.    fe_sub: class(f) + 2 (g must be class 1).
 //   fe_sub4:         class(f) + 4 (g < class 4).     fe_carry: any class <= 7.9 -> class 1.
 // Compiled with -DEG_BOUNDCHECK on the host (tests/hostcheck) every fe carries its class and each
 // operation asserts its precondition, so any executed code path is a proof of the discipline.
@@ -253,6 +254,67 @@ EG_HD void fe_sq(fe& h, const fe& f) {
   }
   h = r;
 #undef EG_SQ_TERMS
+  EG_SCHED_FENCE();
+}
+
+// the value 1 in a scalar register that the compiler cannot see through: x * 1 + carry then stays ONE v_mad_u64_u32 (the 64-bit
+// addition it would otherwise become is two VOP3-priced instructions, profiles/r03_ubench_valu_rates.txt)
+EG_HD u32 fe_opaque_one() {
+  u32 one = 1u;
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(EG_NO_SEED_FENCE)
+  asm("" : "+s"(one));
+#endif
+  return one;
+}
+
+// h = 2 f^2 + 4p - g, class 1: the F = 2 Z^2 - G of a doubling (ge_dbl_chain) without fe_add, fe_sub4 and fe_carry.
+// The squaring holds every limb plain (f) and doubled (d); one more doubling of five limbs (q = 4 f) lets every term of 2 f^2 be ONE
+// product again: diagonal d_i f_i (d_i d_i where the position carries a factor 2), cross terms d_i d_j (d_i q_j).  Limb k of 4p - g
+// seeds low column k ahead of its first product, so the carry chain of the squaring reduces the difference as it goes.
+// Bounds.  The column sums are those of fe_sq times 2, i.e. of fe_mul at class product 2 class(f)^2: 0.078125 * 2 class(f)^2 * 2^64,
+// so 2 class(f)^2 <= 12.5, class(f) <= 2.5 (0.9766 * 2^64; the seeds add less than 2^32 per column, 2^-32 of the sum); d and q stay
+// below 2.51 * 2^30.  g must be below class 4, as in fe_sub4 (limb k of 4p - g does not go negative).  The final carry is < 2^36 as in
+// fe_mul, so limb 1 of the class-1 result is the same hair above its width.  Counts as ONE squaring in the work model.
+EG_HD void fe_sq2_sub(fe& h, const fe& f, const fe& g) {
+  EG_REQUIRE(2.0f * EG_GETCLS(f) * EG_GETCLS(f) <= 12.5f, "fe_sq2_sub: 2 * class(f)^2 > 12.5 (f above class 2.5)");
+  EG_REQUIRE(EG_GETCLS(g) <= 3.9f, "fe_sq2_sub: subtrahend class too large");
+  fe_check_values(f); fe_check_values(g);
+  EG_COUNT_SQ();
+  EG_SCHED_FENCE();
+  u32 d[EG_NL], q[EG_NL], s[EG_NL];
+#pragma unroll
+  for (int i = 0; i < EG_NL; ++i) {
+    d[i] = fe_twice(f.v[i]);
+    q[i] = (i % 3 != 0 && i != 1) ? fe_twice(d[i]) : 0u;       // only limbs 2, 4, 5, 7, 8 are the j of a doubled cross term
+    s[i] = ((4u << fe_w(i)) - (i == 0 ? 76u : 4u)) - g.v[i];   // limb i of 4p - g
+  }
+  const u32 one = fe_opaque_one();
+#define EG_SQ2_TERMS(K)                                                                                     \
+  _Pragma("unroll") for (int i = 0; i < EG_NL; ++i) {                                                       \
+    const int j = (K) - i;                                                                                  \
+    if (j < i || j >= EG_NL) continue;                                                                      \
+    if (i == j) acc += (u64)d[i] * (fe_dbl(i, i) ? d[i] : f.v[i]);                                          \
+    else acc += (u64)d[i] * (fe_dbl(i, j) ? q[j] : d[j]);            /* cross terms count twice */          \
+    EG_SEED_FENCE(acc);                                                                                     \
+  }
+  u64 hc[EG_NL - 1];
+#pragma unroll
+  for (int k = EG_NL; k < 2 * EG_NL - 1; ++k) {
+    u64 acc = 0;
+    EG_SQ2_TERMS(k)
+    hc[k - EG_NL] = acc;
+  }
+  fe r;
+  {
+    fe& h = r;
+    EG_FE_COLUMNS_LOW(
+      if (k == 0) acc = s[0];
+      else { acc += (u64)s[k] * one; EG_SEED_FENCE(acc); }
+      EG_SQ2_TERMS(k)
+    )
+  }
+  h = r;
+#undef EG_SQ2_TERMS
   EG_SCHED_FENCE();
 }
 

@@ -128,6 +128,38 @@ EG_HD void ge_dbl(ge_p1p1& r, const fe& X, const fe& Y, const fe& Z) {
   fe_sub4(r.T, b2, r.Z);              // F = 2ZZ - G [6]
   fe_carry(r.T);                      // [1]
 }
+// The doubling of the chains (table builders, comb columns): ge_dbl with F = 2 Z^2 - G out of ONE fused squaring (fe_sq2_sub) instead
+// of fe_sq, fe_add, fe_sub4 and fe_carry.  Needs Z of class <= 2.5 (every chain hands over [1], or the [2] of a table entry's 2Z);
+// X, Y as in ge_dbl.  Same classes out: {X [5], Y [2], Z [3], T [1]}, same values mod p.
+// negx: doubles (-X : Y : Z) instead, i.e. the NEGATED point.  A doubling reads the sign of X only in (X + Y)^2, so the negation is
+// the choice between Y + X and Y + 2p - X [3], made limb by limb without a select: 2p_i - x = (x ^ ~0) + (2p_i + 1) mod 2^32.
+EG_HD void ge_dbl_chain_sgn(ge_p1p1& r, const fe& X, const fe& Y, const fe& Z, bool negx) {
+  EG_REQUIRE(EG_GETCLS(X) <= 1.02f, "ge_dbl_chain_sgn: X must be class 1");
+  fe xx, yy, a;
+  fe_sq(xx, X);
+  fe_sq(yy, Y);
+  const u32 m = negx ? ~0u : 0u;
+  const u32 k0 = m & ((2u << 29) - 37u), k29 = m & ((2u << 29) - 1u), k28 = m & ((2u << 28) - 1u);
+#pragma unroll
+  for (int i = 0; i < EG_NL; ++i) a.v[i] = Y.v[i] + (X.v[i] ^ m) + (i == 0 ? k0 : fe_w(i) == 29 ? k29 : k28);
+  EG_SETCLS(a, EG_GETCLS(Y) + 2.0f);
+  fe_sq(a, a);                        // AA [1]
+  fe_add(r.Y, yy, xx);                // H [2]
+  fe_sub(r.Z, yy, xx);                // G [3]
+  fe_sub4(r.X, a, r.Y);               // E = AA - H [5]
+  fe_sq2_sub(r.T, Z, r.Z);            // F = 2ZZ - G [1]
+}
+EG_HD void ge_dbl_chain(ge_p1p1& r, const fe& X, const fe& Y, const fe& Z) {
+  fe xx, yy, a;
+  fe_sq(xx, X);
+  fe_sq(yy, Y);
+  fe_add(a, X, Y);                    // [2]
+  fe_sq(a, a);                        // AA [1]
+  fe_add(r.Y, yy, xx);                // H [2]
+  fe_sub(r.Z, yy, xx);                // G [3]
+  fe_sub4(r.X, a, r.Y);               // E = AA - H [5]
+  fe_sq2_sub(r.T, Z, r.Z);            // F = 2ZZ - G [1]
+}
 
 // full-width helpers (not on the hot loop)
 EG_HD void ge_add_full(ge& r, const ge& p, const ge& q) {
@@ -506,7 +538,7 @@ EG_HD void ge_teeth_tables_build(TableIO& io, TmpIO& tmp, const ge& p) {
       ge_add_to_p3(sum, t);
     }
     ge q3;
-    ge_dbl(t, cur.X, cur.Y, cur.Z);
+    ge_dbl_chain(t, cur.X, cur.Y, cur.Z);
     ge_dbl_to_p3(q3, t);                  // 2 P_j, the step of the Gray-code walk for tooth j
     {
       ge_cached qc; ge_to_cached_lazy(qc, q3);
@@ -515,8 +547,8 @@ EG_HD void ge_teeth_tables_build(TableIO& io, TmpIO& tmp, const ge& p) {
     ge_p2 q;
     q.X = q3.X; q.Y = q3.Y; q.Z = q3.Z;
 #pragma unroll 1
-    for (int r = 0; r < Teeth<T>::COLS - 2; ++r) { ge_dbl(t, q.X, q.Y, q.Z); ge_dbl_to_p2(q, t); }
-    ge_dbl(t, q.X, q.Y, q.Z);
+    for (int r = 0; r < Teeth<T>::COLS - 2; ++r) { ge_dbl_chain(t, q.X, q.Y, q.Z); ge_dbl_to_p2(q, t); }
+    ge_dbl_chain(t, q.X, q.Y, q.Z);
     ge_dbl_to_p3(cur, t);                 // P_(j+1)
   }
   {
@@ -634,16 +666,20 @@ EG_HD void ge_teeth_sum_accumulate(AccIO& acc_io, int t, bool first, int m, SrcF
 // acc = [k]P from the teeth table; rows = sc_recode_teeth(k) (consumed).  A column's entry is requested before the doubling and
 // used after it, which hides the load without a second entry buffer (requesting it a whole column ahead, in a second register
 // buffer, measured -0.4 % in round 1 and +-0.2 % = nothing in round 2, when the kernel had the 40 registers to spare).
-// The first column is not added to the identity: +-entry = (Y+X, Y-X, 2Z, ..) IS the point (2X : 2Y : 2Z) in projective
+// The first column is not added to the identity: the entry (Y+X, Y-X, 2Z, ..) IS the point (2X : 2Y : 2Z) in projective
 // coordinates, and the operation that follows is a doubling, which does not read T (saves one 8-multiplication addition).
+// The sign of a column sits on the ACCUMULATOR, never on the entry: with A_c = 2 A_(c+1) + s_c E_c and A'_c = s_c A_c the recurrence
+// is A'_c = 2 (s_c s_(c+1)) A'_(c+1) + E_c, so the accumulator is negated ahead of a doubling when adjacent signs differ (one choice
+// between Y + X and Y - X inside the doubling, ge_dbl_chain_sgn) and the entry is added as it is stored (no 27-limb conditional
+// negation per column).  The result is negated once at the end when s_0 = -1: E of the last addition, which X = E F and T = E H share.
 template <int T, class TableIO>
 EG_HD void ge_teeth_mul(ge& acc, TableIO& io, u64 rows[T]) {
+  bool sgn;                                               // the accumulator holds s * A, s = -1 when set
   {
-    int idx; bool neg;
-    sc_teeth_next<T>(rows, idx, neg);
+    int idx;
+    sc_teeth_next<T>(rows, idx, sgn);
     ge_cached cur;
     io.load(cur, idx);
-    fe t = cur.YpX; fe_cmov(cur.YpX, cur.YmX, neg); fe_cmov(cur.YmX, t, neg);   // -(x, y) = (-x, y)
     fe_sub4(acc.X, cur.YpX, cur.YmX); fe_carry(acc.X);    // 2X
     fe_add(acc.Y, cur.YpX, cur.YmX); fe_carry(acc.Y);     // 2Y
     acc.Z = cur.Z2;                                       // 2Z [2]
@@ -655,14 +691,17 @@ EG_HD void ge_teeth_mul(ge& acc, TableIO& io, u64 rows[T]) {
     ge_cached cur;
     io.load(cur, idx);
     ge_p1p1 t;
-    ge_dbl(t, acc.X, acc.Y, acc.Z);
+    ge_dbl_chain_sgn(t, acc.X, acc.Y, acc.Z, neg != sgn);
+    sgn = neg;
     ge_dbl_to_p3(acc, t);
-    ge_cached_cneg(cur, neg);
     ge_add(t, acc, cur);
     if (c > 0) {                          // next operation is a doubling: T is not needed (saves one multiplication)
       ge_p2 q; ge_add_to_p2(q, t);
       acc.X = q.X; acc.Y = q.Y; acc.Z = q.Z;
     } else {
+      fe n; fe_0(n); EG_SETCLS(n, 0.0f);
+      fe_sub4(n, n, t.X);                 // -E [4]: 4 x 3 (F) and 4 x 2 (H) are inside fe_mul's 12.5
+      fe_cmov(t.X, n, sgn);
       ge_add_to_p3(acc, t);
     }
   }
@@ -678,7 +717,7 @@ EG_HD void ge_teeth_mul_multi(ge& acc, int n_terms, ColumnFn column, LoadFn load
   for (int c = Teeth<T>::COLS - 1; c >= 0; --c) {
     ge_p1p1 t;
     if (c != Teeth<T>::COLS - 1) {
-      ge_dbl(t, acc.X, acc.Y, acc.Z);
+      ge_dbl_chain(t, acc.X, acc.Y, acc.Z);
       ge_dbl_to_p3(acc, t);
     }
 #pragma unroll 1
@@ -738,6 +777,14 @@ EG_HD int ge_fixed_index(int i, int d, int bits) {
   const int ad = d < 0 ? -d : d;
   return i * comb_entries(bits) + (ad == 0 ? 0 : ad - 1);
 }
+// true when the predicate holds in some active lane of the wave (on the host: in this one)
+EG_HD bool eg_wave_any(bool pred) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_amdgcn_ballot_w64(pred) != 0;
+#else
+  return pred;
+#endif
+}
 // io.bits = window width of the table behind io
 template <class NielsIO>
 EG_HD void ge_fixed_mul_add(ge& acc, NielsIO& io, const u32 k[EG_COMB_WORDS]) {
@@ -755,7 +802,10 @@ EG_HD void ge_fixed_mul_add(ge& acc, NielsIO& io, const u32 k[EG_COMB_WORDS]) {
       d_nxt = sc_comb_digit(k, i + 1, carry, bits);
       io.load(nxt, ge_fixed_index(i + 1, d_nxt, bits));
     }
-    fe_cmov(c.ypx, ident.ypx, d == 0); fe_cmov(c.ymx, ident.ymx, d == 0); fe_cmov(c.xy2d, ident.xy2d, d == 0);
+    if (eg_wave_any(d == 0)) {            // a zero digit (one window in 2^bits of a random scalar): the identity, selected only
+      fe_cmov(c.ypx, ident.ypx, d == 0);  // when some lane of the wave needs it; the branch is wave-uniform
+      fe_cmov(c.ymx, ident.ymx, d == 0); fe_cmov(c.xy2d, ident.xy2d, d == 0);
+    }
     ge_niels_cneg(c, d < 0);
     ge_p1p1 t; ge_madd(t, acc, c);
     ge_add_to_p3(acc, t);
