@@ -20,7 +20,7 @@ import os
 from pathlib import Path
 
 __all__ = [
-    "Context", "Ristretto", "ChoiceParams", "QuadraticVotingParams", "PublicKeyVerifier", "DecryptionShareVerifier", "SumOfSquaresVerifier", "EgError", "library_path", "build",
+    "Context", "Ristretto", "Ed25519", "ChoiceParams", "QuadraticVotingParams", "PublicKeyVerifier", "DecryptionShareVerifier", "SumOfSquaresVerifier", "EgError", "library_path", "build",
     "STATUS_NAMES", "status_kind", "status_detail", "pack_json", "JsonPacker", "PACK_RESHAPE", "verify_json_multi", "json_stream_multi",
 ]
 
@@ -36,6 +36,7 @@ STATUS_NAMES = {
     5: "Range(LenMismatch)", 6: "Range(ChallengeMismatch)", 7: "Variant(LenMismatch)", 8: "Variant(ChallengeMismatch)",
     9: "CreditRange(LenMismatch)", 10: "CreditRange(ChallengeMismatch)", 11: "CreditEquivalence(LenMismatch)",
     12: "CreditEquivalence(ChallengeMismatch)", 13: "Malformed", 14: "Duplicate",
+    15: "BadSignature",
 }
 
 
@@ -202,6 +203,15 @@ def _load() -> C.CDLL:
         "eg_qv_weed_scratch_bytes": (sz, [vp, sz, sz]),
         "eg_qv_weed_device": (C.c_int, [vp, sz, vp, vp, sz, vp, sz, C.c_uint64, vp, vp, vp, vp, vp, vp]),
         "eg_qv_weed": (C.c_int, [vp, sz, vp, vp, sz, vp, vp, vp, vp, C.POINTER(sz)]),
+        "eg_ed25519_verify_scratch_bytes": (sz, [vp, sz]),
+        "eg_ed25519_verify_device": (C.c_int, [vp, sz, vp, sz, sz, cp, sz, vp, sz, vp, vp, vp, vp, vp, sz, vp]),
+        "eg_ed25519_verify_batch": (C.c_int, [vp, sz, cp, sz, sz, cp, sz, cp, sz, vp, cp, vp, vp]),
+        "eg_ed25519_keypair_batch": (C.c_int, [vp, sz, cp, cp]),
+        "eg_ed25519_keypair_batch_device": (C.c_int, [vp, sz, vp, vp, vp]),
+        "eg_ed25519_sign_batch": (C.c_int, [vp, sz, cp, cp, sz, sz, cp, sz, cp]),
+        "eg_ed25519_sign_batch_device": (C.c_int, [vp, sz, vp, vp, sz, sz, vp, sz, vp, vp]),
+        "eg_sha512_batch": (C.c_int, [vp, sz, cp, sz, sz, cp, sz, cp]),
+        "eg_sha512_batch_device": (C.c_int, [vp, sz, vp, sz, sz, vp, sz, vp, vp]),
         "eg_proof_params_create": (C.c_int, [vp, cp, C.c_int, C.c_uint64, C.POINTER(vp)]),
         "eg_share_params_create": (C.c_int, [vp, cp, C.c_uint64, C.c_uint64, C.c_uint64, cp, C.POINTER(vp)]),
         "eg_proof_params_destroy": (None, [vp]),
@@ -271,6 +281,8 @@ ST_DUPLICATE = 14                # include/eg_hip.h: EG_ST_DUPLICATE, what weed(
 DUP_NONE = 0xFFFFFFFF            # include/eg_hip.h: EG_DUP_NONE
 DUP_PRIOR = 0xFFFFFFFE           # include/eg_hip.h: EG_DUP_PRIOR, a ballot that repeats a ciphertext of the board
 WEED_KEYS_MAX = 1 << 30          # include/eg_hip.h: EG_WEED_KEYS_MAX
+ST_BAD_SIGNATURE = 15            # include/eg_hip.h: EG_ST_BAD_SIGNATURE, what Ed25519.verify writes; the detail is one of ED25519_*
+ED25519_BAD_S, ED25519_BAD_KEY, ED25519_SMALL_ORDER, ED25519_MISMATCH, ED25519_BAD_INDEX = 1, 2, 3, 4, 5
 
 
 def pack_json(text, n_options: int, single: bool | None = None, credits: int | None = None, threads: int = 0, max_objects: int = 0):
@@ -550,6 +562,83 @@ class Ristretto:
                                  d_ok: int = 0, stream: int = 0):
         """The multi-scalar multiplication on device buffers, asynchronous on `stream` (eg_vartime_multi_mul_batch_device)."""
         _check(_load().eg_vartime_multi_mul_batch_device(self.ctx._h, n, terms, d_scalars, d_points, d_r, d_scratch, d_out, d_ok, stream))
+
+
+class Ed25519:
+    """Voter signatures: Ed25519 (RFC 8032, pure EdDSA) of a batch in one pass (include/eg_hip.h, "voter signatures" has the rule).
+    Item b signs prefix || msgs[b * stride : b * stride + msg_len] under keys[b], or under keys[key_index[b]] out of a roster.
+    The signer (keypairs, sign) is VARIABLE TIME: a maker of test and benchmark items, not for a voter client."""
+
+    def __init__(self, ctx: Context):
+        self.ctx = ctx
+
+    @staticmethod
+    def _n(msgs: bytes, msg_len: int, stride, n):
+        stride = msg_len if stride is None else stride
+        if n is None:
+            if stride == 0:
+                raise EgError("n is needed for messages of length 0")
+            n = (len(msgs) + stride - msg_len) // stride
+        return n, stride
+
+    def keypairs(self, seeds: bytes) -> bytes:
+        """Public keys (32 bytes each) of the 32-byte seeds."""
+        n = len(seeds) // 32
+        out = C.create_string_buffer(32 * n)
+        _check(_load().eg_ed25519_keypair_batch(self.ctx._h, n, seeds, out))
+        return out.raw
+
+    def sign(self, seeds: bytes, msgs: bytes, msg_len: int, prefix: bytes = b"", stride=None) -> bytes:
+        """Signatures (64 bytes each): item b is signed under seeds[b]."""
+        n = len(seeds) // 32
+        _, stride = self._n(msgs, msg_len, stride, n)
+        out = C.create_string_buffer(64 * n)
+        _check(_load().eg_ed25519_sign_batch(self.ctx._h, n, seeds, msgs, stride, msg_len, prefix or None, len(prefix), out))
+        return out.raw
+
+    def verify(self, msgs: bytes, msg_len: int, keys: bytes, sigs: bytes, prefix: bytes = b"", key_index=None, status_in=None, stride=None):
+        """Status words of the n = len(sigs) / 64 items: 0, or ST_BAD_SIGNATURE with the failed check in status_detail; a non-zero word
+        of status_in is handed on and that item is not looked at."""
+        import array
+
+        n = len(sigs) // 64
+        _, stride = self._n(msgs, msg_len, stride, n)
+        idx = (C.c_uint32 * n)(*key_index) if key_index is not None else None
+        sin = (C.c_uint32 * n)(*status_in) if status_in is not None else None
+        out = (C.c_uint32 * max(n, 1))()
+        _check(_load().eg_ed25519_verify_batch(self.ctx._h, n, msgs, stride, msg_len, prefix or None, len(prefix), keys, len(keys) // 32, idx, sigs,
+                                               sin, out))
+        return array.array("I", out[:n]).tolist()
+
+    def verify_scratch_bytes(self, n: int) -> int:
+        return int(_load().eg_ed25519_verify_scratch_bytes(self.ctx._h, n))
+
+    def verify_device(self, n: int, d_msgs: int, msg_stride: int, msg_len: int, d_keys: int, n_keys: int, d_sigs: int, d_status_out: int,
+                      d_scratch: int, scratch_bytes: int, prefix: bytes = b"", d_key_index: int = 0, d_status_in: int = 0, stream: int = 0):
+        """Asynchronous device-pointer variant (eg_ed25519_verify_device): no allocation, no host synchronisation, no lock.  `prefix` is
+        host bytes; d_scratch: verify_scratch_bytes(n) bytes; d_status_out may be d_status_in."""
+        _check(_load().eg_ed25519_verify_device(self.ctx._h, n, d_msgs or None, msg_stride, msg_len, prefix or None, len(prefix), d_keys or None,
+                                                n_keys, d_key_index or None, d_sigs or None, d_status_in or None, d_status_out or None,
+                                                d_scratch or None, scratch_bytes, stream or None))
+
+    def keypairs_device(self, n: int, d_seeds: int, d_keys: int, stream: int = 0):
+        _check(_load().eg_ed25519_keypair_batch_device(self.ctx._h, n, d_seeds or None, d_keys or None, stream or None))
+
+    def sign_device(self, n: int, d_seeds: int, d_msgs: int, msg_stride: int, msg_len: int, d_sigs: int, d_prefix: int = 0, prefix_len: int = 0,
+                    stream: int = 0):
+        _check(_load().eg_ed25519_sign_batch_device(self.ctx._h, n, d_seeds or None, d_msgs or None, msg_stride, msg_len, d_prefix or None,
+                                                    prefix_len, d_sigs or None, stream or None))
+
+    def sha512(self, msgs: bytes, msg_len: int, prefix: bytes = b"", stride=None, n=None) -> bytes:
+        """SHA-512(prefix || msg_b) of n messages of one length: 64 bytes each."""
+        n, stride = self._n(msgs, msg_len, stride, n)
+        out = C.create_string_buffer(64 * max(n, 1))
+        _check(_load().eg_sha512_batch(self.ctx._h, n, msgs, stride, msg_len, prefix or None, len(prefix), out))
+        return out.raw[: 64 * n]
+
+    def sha512_device(self, n: int, d_msgs: int, msg_stride: int, msg_len: int, d_digests: int, d_prefix: int = 0, prefix_len: int = 0, stream: int = 0):
+        _check(_load().eg_sha512_batch_device(self.ctx._h, n, d_msgs or None, msg_stride, msg_len, d_prefix or None, prefix_len, d_digests or None,
+                                              stream or None))
 
 
 def prepared_point_size() -> int:

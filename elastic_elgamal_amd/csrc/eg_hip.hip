@@ -34,6 +34,7 @@
 #include "group_tally_kernels.cuh"
 #include "share_combine_kernels.cuh"
 #include "weed_kernels.cuh"
+#include "ed25519_kernels.cuh"
 
 using namespace eg;
 
@@ -4033,6 +4034,176 @@ int eg_merlin_challenge_batch(eg_ctx* c, size_t n, const char* proto, size_t pro
   TRY(o.get(out, n * out_len, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   HIPCHK(hipGetLastError());
+  return EG_OK;
+}
+
+// ---- voter signatures: Ed25519 of a batch (ed25519_kernels.cuh; the rule: include/eg_hip.h) -------------------------------------------
+// Stateless like weeding: the generator's comb is immutable once the context exists, everything else is the caller's - no lock, no
+// workspace of the context.
+// The argument rules come first and need no context (so they can be tested without a GPU); what passes them fails on a null context.
+static int ed_check_messages(size_t n, const void* msgs, size_t msg_stride, size_t msg_len, const void* prefix, size_t prefix_len) {
+  if (const char* why = eged::refuse_messages(n, msgs != nullptr, msg_stride, msg_len, prefix != nullptr, prefix_len))
+    return fail(EG_ERR_BAD_ARG, std::string("ed25519: ") + why);
+  return EG_OK;
+}
+static int ed_check_ctx(const eg_ctx* c) { return c ? EG_OK : fail(EG_ERR_BAD_ARG, "ed25519: null ctx"); }
+static int ed_check_roster(size_t n, const void* keys, size_t n_keys, const void* key_index, const void* sigs, const void* status_out) {
+  if (n && (!keys || !sigs || !status_out)) return fail(EG_ERR_BAD_ARG, "ed25519: null keys, sigs or status_out");
+  if (const char* why = eged::refuse_roster(n, n_keys, key_index != nullptr)) return fail(EG_ERR_BAD_ARG, std::string("ed25519: ") + why);
+  return EG_OK;
+}
+size_t eg_ed25519_verify_scratch_bytes(const eg_ctx* c, size_t n) {
+  return c && n < eged::N_LIMIT ? eged::layout(n, (unsigned)c->cus).total : 0;
+}
+int eg_ed25519_verify_device(eg_ctx* c, size_t n, const void* d_msgs, size_t msg_stride, size_t msg_len, const uint8_t* prefix, size_t prefix_len,
+                             const void* d_keys, size_t n_keys, const void* d_key_index, const void* d_sigs, const void* d_status_in,
+                             void* d_status_out, void* d_scratch, size_t scratch_bytes, void* stream) {
+  TRY_(ed_check_messages(n, d_msgs, msg_stride, msg_len, prefix, prefix_len));
+  TRY_(ed_check_roster(n, d_keys, n_keys, d_key_index, d_sigs, d_status_out));
+  if (((uintptr_t)d_keys | (uintptr_t)d_sigs | (uintptr_t)d_key_index | (uintptr_t)d_status_in | (uintptr_t)d_status_out) & 3u)
+    return fail(EG_ERR_BAD_ARG, "ed25519: keys, sigs, key_index and the status arrays must be 4-byte aligned");
+  TRY_(ed_check_ctx(c));
+  if (n == 0) return EG_OK;
+  const eged::Layout L = eged::layout(n, (unsigned)c->cus);
+  if (!d_scratch || scratch_bytes < L.total) return fail(EG_ERR_BAD_ARG, "ed25519: scratch is null or too small (eg_ed25519_verify_scratch_bytes says how much)");
+  if ((uintptr_t)d_scratch & 15u) return fail(EG_ERR_BAD_ARG, "ed25519: scratch must be 16-byte aligned");
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)stream;
+  char* base = static_cast<char*>(d_scratch);
+  if (prefix_len) HIPCHK(hipMemcpyAsync(base + L.prefix, prefix, prefix_len, hipMemcpyHostToDevice, s));
+  const EdItems it{static_cast<const unsigned char*>(d_msgs), msg_stride, msg_len, reinterpret_cast<const unsigned char*>(base + L.prefix), prefix_len};
+  const EdRoster ro{static_cast<const u32*>(d_keys), n_keys, static_cast<const u32*>(d_key_index)};
+  u32* h = reinterpret_cast<u32*>(base + L.h);
+  hipLaunchKernelGGL(k_ed25519_hash, dim3(blocks_of(n)), dim3(NT), 0, s, n, it, ro, static_cast<const u32*>(d_sigs), static_cast<const u32*>(d_status_in), h);
+  hipLaunchKernelGGL(k_ed25519_verify, dim3(L.blocks), dim3(NT), 0, s, n, ro, static_cast<const u32*>(d_sigs), (const u32*)h,
+                     static_cast<const u32*>(d_status_in), static_cast<u32*>(d_status_out), (const uint4*)c->tabG,
+                     reinterpret_cast<uint4*>(base + L.tables));
+  HIPCHK(hipGetLastError());
+  return EG_OK;
+}
+// host staging of the Ed25519 entries: device buffers and a stream of the call's own
+struct EdStage {
+  std::vector<void*> bufs;
+  hipStream_t s = nullptr;
+  ~EdStage() {
+    for (void* p : bufs) if (p) (void)hipFree(p);
+    if (s) (void)hipStreamDestroy(s);
+  }
+  int open() { HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); return EG_OK; }
+  int put(void** out, const void* src, size_t bytes) {        // src null: room only
+    void* p = nullptr;
+    const hipError_t he = hipMalloc(&p, std::max<size_t>(bytes, 16));
+    if (he == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(EG_ERR_NOMEM, "ed25519: the staging buffers do not fit the device memory"); }
+    HIPCHK(he);
+    bufs.push_back(p);
+    if (src && bytes) HIPCHK(hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, s));
+    *out = p;
+    return EG_OK;
+  }
+};
+static size_t ed_msgs_bytes(size_t n, size_t msg_stride, size_t msg_len) { return n ? (n - 1) * msg_stride + msg_len : 0; }
+int eg_ed25519_verify_batch(eg_ctx* c, size_t n, const uint8_t* msgs, size_t msg_stride, size_t msg_len, const uint8_t* prefix, size_t prefix_len,
+                            const uint8_t* keys, size_t n_keys, const uint32_t* key_index, const uint8_t* sigs, const uint32_t* status_in,
+                            uint32_t* status_out) {
+  TRY_(ed_check_messages(n, msgs, msg_stride, msg_len, prefix, prefix_len));
+  TRY_(ed_check_roster(n, keys, n_keys, key_index, sigs, status_out));
+  TRY_(ed_check_ctx(c));
+  if (n == 0) return EG_OK;
+  HIPCHK(hipSetDevice(c->device));
+  EdStage st; TRY_(st.open());
+  const size_t need = eg_ed25519_verify_scratch_bytes(c, n);
+  void *dm, *dk, *di = nullptr, *ds, *dsi = nullptr, *dso, *scratch;
+  TRY_(st.put(&dm, msgs, ed_msgs_bytes(n, msg_stride, msg_len)));
+  TRY_(st.put(&dk, keys, n_keys * 32));
+  if (key_index) TRY_(st.put(&di, key_index, n * 4));
+  TRY_(st.put(&ds, sigs, n * 64));
+  if (status_in) TRY_(st.put(&dsi, status_in, n * 4));
+  TRY_(st.put(&dso, nullptr, n * 4));
+  TRY_(st.put(&scratch, nullptr, need));
+  TRY_(eg_ed25519_verify_device(c, n, dm, msg_stride, msg_len, prefix, prefix_len, dk, n_keys, di, ds, dsi, dso, scratch, need, st.s));
+  HIPCHK(hipMemcpyAsync(status_out, dso, n * 4, hipMemcpyDeviceToHost, st.s));
+  HIPCHK(hipStreamSynchronize(st.s));
+  return EG_OK;
+}
+int eg_ed25519_keypair_batch_device(eg_ctx* c, size_t n, const void* d_seeds, void* d_keys, void* stream) {
+  if (n >= eged::N_LIMIT) return fail(EG_ERR_BAD_ARG, "ed25519: n is 2^31 or more");
+  if ((n && (!d_seeds || !d_keys)) || ((uintptr_t)d_keys & 3u)) return fail(EG_ERR_BAD_ARG, "ed25519: null seeds or keys, or keys not 4-byte aligned");
+  TRY_(ed_check_ctx(c));
+  if (n == 0) return EG_OK;
+  HIPCHK(hipSetDevice(c->device));
+  hipLaunchKernelGGL(k_ed25519_keypair, dim3(blocks_of(n)), dim3(NT), 0, (hipStream_t)stream, n, static_cast<const unsigned char*>(d_seeds),
+                     (const uint4*)c->tabG, static_cast<u32*>(d_keys));
+  HIPCHK(hipGetLastError());
+  return EG_OK;
+}
+int eg_ed25519_keypair_batch(eg_ctx* c, size_t n, const uint8_t* seeds, uint8_t* keys) {
+  if (n >= eged::N_LIMIT) return fail(EG_ERR_BAD_ARG, "ed25519: n is 2^31 or more");
+  if (n && (!seeds || !keys)) return fail(EG_ERR_BAD_ARG, "ed25519: null seeds or keys");
+  TRY_(ed_check_ctx(c));
+  if (n == 0) return EG_OK;
+  HIPCHK(hipSetDevice(c->device));
+  EdStage st; TRY_(st.open());
+  void *dse, *dk;
+  TRY_(st.put(&dse, seeds, n * 32)); TRY_(st.put(&dk, nullptr, n * 32));
+  TRY_(eg_ed25519_keypair_batch_device(c, n, dse, dk, st.s));
+  HIPCHK(hipMemcpyAsync(keys, dk, n * 32, hipMemcpyDeviceToHost, st.s));
+  HIPCHK(hipStreamSynchronize(st.s));
+  return EG_OK;
+}
+int eg_ed25519_sign_batch_device(eg_ctx* c, size_t n, const void* d_seeds, const void* d_msgs, size_t msg_stride, size_t msg_len,
+                                 const void* d_prefix, size_t prefix_len, void* d_sigs, void* stream) {
+  TRY_(ed_check_messages(n, d_msgs, msg_stride, msg_len, d_prefix, prefix_len));
+  if ((n && (!d_seeds || !d_sigs)) || ((uintptr_t)d_sigs & 3u)) return fail(EG_ERR_BAD_ARG, "ed25519: null seeds or sigs, or sigs not 4-byte aligned");
+  TRY_(ed_check_ctx(c));
+  if (n == 0) return EG_OK;
+  HIPCHK(hipSetDevice(c->device));
+  const EdItems it{static_cast<const unsigned char*>(d_msgs), msg_stride, msg_len, static_cast<const unsigned char*>(d_prefix), prefix_len};
+  hipLaunchKernelGGL(k_ed25519_sign, dim3(blocks_of(n)), dim3(NT), 0, (hipStream_t)stream, n, static_cast<const unsigned char*>(d_seeds), it,
+                     (const uint4*)c->tabG, static_cast<u32*>(d_sigs));
+  HIPCHK(hipGetLastError());
+  return EG_OK;
+}
+int eg_ed25519_sign_batch(eg_ctx* c, size_t n, const uint8_t* seeds, const uint8_t* msgs, size_t msg_stride, size_t msg_len, const uint8_t* prefix,
+                          size_t prefix_len, uint8_t* sigs) {
+  TRY_(ed_check_messages(n, msgs, msg_stride, msg_len, prefix, prefix_len));
+  if (n && (!seeds || !sigs)) return fail(EG_ERR_BAD_ARG, "ed25519: null seeds or sigs");
+  TRY_(ed_check_ctx(c));
+  if (n == 0) return EG_OK;
+  HIPCHK(hipSetDevice(c->device));
+  EdStage st; TRY_(st.open());
+  void *dse, *dm, *dp, *dsg;
+  TRY_(st.put(&dse, seeds, n * 32)); TRY_(st.put(&dm, msgs, ed_msgs_bytes(n, msg_stride, msg_len)));
+  TRY_(st.put(&dp, prefix, prefix_len)); TRY_(st.put(&dsg, nullptr, n * 64));
+  TRY_(eg_ed25519_sign_batch_device(c, n, dse, dm, msg_stride, msg_len, dp, prefix_len, dsg, st.s));
+  HIPCHK(hipMemcpyAsync(sigs, dsg, n * 64, hipMemcpyDeviceToHost, st.s));
+  HIPCHK(hipStreamSynchronize(st.s));
+  return EG_OK;
+}
+int eg_sha512_batch_device(eg_ctx* c, size_t n, const void* d_msgs, size_t msg_stride, size_t msg_len, const void* d_prefix, size_t prefix_len,
+                           void* d_digests, void* stream) {
+  TRY_(ed_check_messages(n, d_msgs, msg_stride, msg_len, d_prefix, prefix_len));
+  if ((n && !d_digests) || ((uintptr_t)d_digests & 3u)) return fail(EG_ERR_BAD_ARG, "sha512: digests null or not 4-byte aligned");
+  TRY_(ed_check_ctx(c));
+  if (n == 0) return EG_OK;
+  HIPCHK(hipSetDevice(c->device));
+  const EdItems it{static_cast<const unsigned char*>(d_msgs), msg_stride, msg_len, static_cast<const unsigned char*>(d_prefix), prefix_len};
+  hipLaunchKernelGGL(k_sha512, dim3(blocks_of(n)), dim3(NT), 0, (hipStream_t)stream, n, it, static_cast<u32*>(d_digests));
+  HIPCHK(hipGetLastError());
+  return EG_OK;
+}
+int eg_sha512_batch(eg_ctx* c, size_t n, const uint8_t* msgs, size_t msg_stride, size_t msg_len, const uint8_t* prefix, size_t prefix_len,
+                    uint8_t* digests) {
+  TRY_(ed_check_messages(n, msgs, msg_stride, msg_len, prefix, prefix_len));
+  if (n && !digests) return fail(EG_ERR_BAD_ARG, "sha512: null digests");
+  TRY_(ed_check_ctx(c));
+  if (n == 0) return EG_OK;
+  HIPCHK(hipSetDevice(c->device));
+  EdStage st; TRY_(st.open());
+  void *dm, *dp, *dd;
+  TRY_(st.put(&dm, msgs, ed_msgs_bytes(n, msg_stride, msg_len))); TRY_(st.put(&dp, prefix, prefix_len)); TRY_(st.put(&dd, nullptr, n * 64));
+  TRY_(eg_sha512_batch_device(c, n, dm, msg_stride, msg_len, dp, prefix_len, dd, st.s));
+  HIPCHK(hipMemcpyAsync(digests, dd, n * 64, hipMemcpyDeviceToHost, st.s));
+  HIPCHK(hipStreamSynchronize(st.s));
   return EG_OK;
 }
 

@@ -1,7 +1,7 @@
 // voting.cpp -- the reference's examples/voting.rs on the GPU backend, in C++ on top of the C ABI:
 //   `Args::vote`            (examples/voting.rs:179-213)  ./voting [votes] [options] [seed]
 //   `Args::quadratic_vote`  (examples/voting.rs:219-269)  ./voting --qv [votes] [options] [credits] [seed]
-//   options: --devices N, --json, --precincts P, --weighted, --replays K
+//   options: --devices N, --json, --precincts P, --weighted, --replays K, --signed K
 // talliers' key -> voters create ballots from their own choices -> verify every ballot -> homomorphic totals -> decrypt and
 // compare with the EXPECTED totals the voters' choices add up to.  Threshold sharing of the key (examples/voting.rs:105-120) is out
 // of scope; a single key pair stands in for the shared key (tests/test_gpu_parity.py::test_threshold_tally_end_to_end
@@ -17,6 +17,10 @@
 // With --replays K, K extra voters resubmit byte-for-byte copies of earlier ballots.  The reference's proofs bind nothing of the voter, so
 // every copy of an accepted ballot verifies; the flow weeds between verify and tally (weed = eg_*_weed: ballots that repeat a ciphertext
 // are flagged), prints the number dropped, tallies what is left (tally_grouped over the weeded status words) and reaches the same totals.
+// With --signed K every voter signs their packed ballot (Ed25519 under the election's prefix) with a key of the voters' roster, and K
+// envelopes are forged: a right signature under another voter's roster index, or a flipped bit.  The signature pass (Ed25519::verify =
+// eg_ed25519_verify_batch) runs before the ballots are verified; its status words are chained with the verifier's, and the K forgeries,
+// and only they, are left out of the tally (tally_grouped over the chained words) - their ballots themselves are perfectly valid.
 //
 //   g++ -std=c++17 -Iinclude examples/voting.cpp -Lelastic_elgamal_amd -leg_hip -Wl,-rpath,$PWD/elastic_elgamal_amd -o voting
 #include <cstdio>
@@ -145,6 +149,53 @@ static bool replayed_tally(const Context& ctx, const Ristretto& group, const Sca
   return ok;
 }
 
+// --signed: every voter signs the packed ballot under a roster key; K envelopes are forged; signature pass -> verify -> tally of the rest
+template <class Params>
+static bool signed_tally(const Context& ctx, const Ristretto& group, const Scalar& sk, const Params& params, const Bytes& ballots, size_t votes,
+                         size_t forgeries, const std::vector<uint32_t>& votes_of, size_t options, uint64_t max_value, uint64_t seed) {
+  const size_t size = params.ballot_size();
+  const Ed25519 ed{ctx};
+  const char* election = "voting.cpp election #1";
+  const Bytes prefix(election, election + strlen(election));
+  Rng rng{seed ^ 0x5167ull};
+  Bytes seeds(32 * votes);
+  for (auto& b : seeds) b = (uint8_t)rng.next();
+  const Bytes roster = ed.keypairs(seeds);                       // the registered voters' keys; voter v holds seed v
+  Bytes sigs = ed.sign(seeds, ballots, size, prefix);
+  std::vector<uint32_t> index(votes);
+  for (size_t v = 0; v < votes; ++v) index[v] = (uint32_t)v;
+  std::vector<bool> forged(votes, false);
+  for (size_t i = 0; i < forgeries; ++i) {
+    const size_t v = votes - 1 - i;
+    forged[v] = true;
+    if (i % 2) index[v] = (uint32_t)((v + 1) % votes);           // somebody else's place in the roster
+    else sigs[64 * v + (i % 64)] ^= 1;                           // a flipped bit
+  }
+  const std::vector<uint32_t> sig_status = ed.verify(ballots, size, roster, sigs, prefix, index);     // BEFORE the ballots are looked at
+  size_t refused = 0;
+  bool ok = true;
+  for (size_t v = 0; v < votes; ++v) {
+    if (sig_status[v]) { ++refused; printf("  voter #%zu refused: bad signature (check %u)\n", v + 1, EG_STATUS_DETAIL(sig_status[v])); }
+    ok = ok && (sig_status[v] != 0) == forged[v] && (!sig_status[v] || EG_STATUS_KIND(sig_status[v]) == EG_ST_BAD_SIGNATURE);
+  }
+  printf("%zu forged envelopes: the signature pass refused %zu of %zu\n", forgeries, refused, votes);
+  const auto verdict = params.verify_batch(ballots);
+  std::vector<uint32_t> chained(votes);
+  std::vector<uint64_t> expected(options, 0);
+  size_t counted = 0;
+  for (size_t v = 0; v < votes; ++v) {
+    chained[v] = sig_status[v] ? sig_status[v] : verdict.results[v] ? 1u : 0u;
+    if (chained[v]) continue;
+    ++counted;
+    for (size_t k = 0; k < options; ++k) expected[k] += votes_of[v * options + k];
+  }
+  const GroupedTally kept = params.tally_grouped(ballots, chained, std::vector<uint32_t>(votes, 0u), 1);
+  ok = ok && refused == forgeries && kept.accepted[0] == counted;
+  ok = tally(ctx, group, sk, kept.totals[0], expected, max_value) && ok;
+  printf("the forgeries%s are left out of the tally\n", ok ? ", and only they," : " and the tally DISAGREE: not only they");
+  return ok;
+}
+
 // serde's human-readable form of an EncryptedChoice (src/serde.rs:19-80: every element and scalar as unpadded base64url; field names of
 // choice.rs:276-280, ring.rs:282-287, log_equality.rs:96-101), from the packed ballot
 static std::string b64url(const uint8_t* p, size_t n) {
@@ -172,7 +223,7 @@ static std::string choice_to_json(const uint8_t* b, size_t options) {
 int main(int argc, char** argv) {
   bool qv = false, json = false, weighted = false;
   int devices = 1;
-  long precincts = 0, replays = 0;
+  long precincts = 0, replays = 0, signed_forgeries = -1;
   std::vector<std::string> pos;
   for (int i = 1; i < argc; ++i) {
     if (!strcmp(argv[i], "--qv")) qv = true;
@@ -181,6 +232,7 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "--devices") && i + 1 < argc) devices = atoi(argv[++i]);
     else if (!strcmp(argv[i], "--precincts") && i + 1 < argc) precincts = atol(argv[++i]);
     else if (!strcmp(argv[i], "--replays") && i + 1 < argc) replays = atol(argv[++i]);
+    else if (!strcmp(argv[i], "--signed") && i + 1 < argc) signed_forgeries = atol(argv[++i]);
     else pos.push_back(argv[i]);
   }
   auto arg = [&](size_t k, uint64_t dflt) { return k < pos.size() ? strtoull(pos[k].c_str(), nullptr, 10) : dflt; };
@@ -188,6 +240,9 @@ int main(int argc, char** argv) {
   const uint64_t credits = qv ? arg(2, 20) : 0, seed = arg(qv ? 3 : 2, 1);
   if (devices < 1 || devices > 16) { printf("--devices must be in 1..16\n"); return 2; }
   if (replays < 0 || replays > 1000000 || (replays && !votes)) { printf("--replays must be in 0..1000000 and needs a voter to copy\n"); return 2; }
+  if (signed_forgeries < -1 || (signed_forgeries >= 0 && (size_t)signed_forgeries > votes) || (signed_forgeries > 0 && votes < 2)) {
+    printf("--signed K needs 0 <= K <= votes and two voters to forge\n"); return 2;
+  }
   if (precincts < 0 || precincts > (long)EG_TALLY_GROUPS_MAX) { printf("--precincts must be in 0..%u\n", EG_TALLY_GROUPS_MAX); return 2; }
 
   // one context per device slot; slot d uses GPU d when the process sees that many, else GPU 0
@@ -250,6 +305,11 @@ int main(int argc, char** argv) {
       for (size_t i = 0; i < votes; ++i) one_hot[i * options + choices[i]] = 1u;
       ok = weighted_tally(ctx, group, sk, *params[0], ballots, verdict, one_hot, options, 1) && ok;
     }
+    if (signed_forgeries >= 0) {
+      std::vector<uint32_t> one_hot(votes * options, 0u);
+      for (size_t i = 0; i < votes; ++i) one_hot[i * options + choices[i]] = 1u;
+      ok = signed_tally(ctx, group, sk, *params[0], ballots, votes, (size_t)signed_forgeries, one_hot, options, votes, seed) && ok;
+    }
     if (replays) ok = replayed_tally(ctx, group, sk, *params[0], ballots, votes, (size_t)replays, expected, votes) && ok;
   } else {
     std::vector<std::unique_ptr<QuadraticVotingParams>> params;
@@ -283,6 +343,7 @@ int main(int argc, char** argv) {
     if (precincts) ok = precinct_tally(ctx, group, sk, *params[0], ballots, verdict, (uint32_t)precincts, expected_by_precinct, expected, max_votes) && ok;
     if (weighted) ok = weighted_tally(ctx, group, sk, *params[0], ballots, verdict, all, options, params[0]->max_votes()) && ok;
     if (replays) ok = replayed_tally(ctx, group, sk, *params[0], ballots, votes, (size_t)replays, expected, max_votes) && ok;
+    if (signed_forgeries >= 0) ok = signed_tally(ctx, group, sk, *params[0], ballots, votes, (size_t)signed_forgeries, all, options, max_votes, seed) && ok;
   }
   printf("%s: the decrypted totals %s the expected ones\n", ok ? "OK" : "MISMATCH", ok ? "equal" : "differ from");
   return ok ? 0 : 1;

@@ -111,8 +111,10 @@ enum {
   EG_ST_QV_CREDIT_EQUIV_CHALLENGE = 12, /* QuadraticVotingError::CreditEquivalence (:343) */
   EG_ST_MALFORMED = 13,           /* the ballot object does not deserialise at all (bad base64url / byte length, fewer than 2
                                      responses, wrong proof kind: serde.rs:29-80,303-355); object-ingest layer only */
-  EG_ST_DUPLICATE = 14            /* no verdict of the reference: an accepted ballot that repeats a tally ciphertext of the board or of an
+  EG_ST_DUPLICATE = 14,           /* no verdict of the reference: an accepted ballot that repeats a tally ciphertext of the board or of an
                                      earlier ballot; written by eg_*_weed* into status_out only, detail 0 */
+  EG_ST_BAD_SIGNATURE = 15        /* no verdict of the reference: the voter's Ed25519 signature over the item does not hold; written by
+                                     eg_ed25519_verify* only, detail = which check failed (EG_ED25519_*) */
 };
 #define EG_STATUS_KIND(s) ((s) & 0xffu)
 #define EG_STATUS_DETAIL(s) ((s) >> 8)
@@ -485,6 +487,66 @@ int eg_qv_weed_device(eg_qv_params*, size_t n, const void* d_ballots, const void
 int eg_qv_weed(eg_qv_params*, size_t n, const uint8_t* ballots, const uint32_t* status /* or NULL */, size_t n_prior,
                const uint8_t* board, uint32_t* dup_of, uint32_t* status_out /* or NULL */,
                uint8_t* appended /* or NULL; room for n * n_options * 64 */, size_t* n_appended);
+
+/* ---- voter signatures: Ed25519 (RFC 8032, pure EdDSA) of a batch checked in one pass ------------------------------------------------
+ * The reference's proofs bind nothing of the voter: a fresh, valid ballot cast by someone who is not on the roll, or in another voter's
+ * name, verifies.  A deployment wraps the ballot in a signature under a registered voter key; this pass checks those signatures where
+ * the ballots already are.  Ed25519 lives on the engine's curve: the Ristretto generator is the Ed25519 base point B.
+ *
+ * THE RULE.  For item b the message is M_b = prefix || msg_b: `prefix` is 0..255 bytes, one per call (domain separation: the election
+ * id); msg_b is msg_len bytes at msgs + b * msg_stride (a packed ballot buffer is passed as it is, msg_stride = msg_len = ballot size).
+ * The key is A_b = keys[b] when key_index is NULL, else keys[key_index[b]] out of a roster of n_keys keys (the voter id selects the
+ * registered key; a signature counts only under that key).  The signature is sig_b = R(32) || S(32).  The checks run in this order,
+ * the first failure wins, and every failure is status EG_ST_BAD_SIGNATURE with the detail in EG_STATUS_DETAIL:
+ *   EG_ED25519_BAD_INDEX   5  key_index[b] >= n_keys
+ *   EG_ED25519_BAD_S       1  S is not canonical (S >= l)
+ *   EG_ED25519_BAD_KEY     2  A does not decode (RFC 8032 5.1.3, STRICT: y >= p is refused, x = 0 with the sign bit set is refused,
+ *                             no square root is refused)
+ *   EG_ED25519_SMALL_ORDER 3  [8]A is the identity
+ *   EG_ED25519_MISMATCH    4  with h = SHA-512(R || A || M_b) mod l and R' = [S]B - [h]A, the RFC 8032 5.1.2 encoding of R' differs from
+ *                             the 32 bytes R
+ * R is never decoded, so a non-canonical R can never match; a small-order R is not separately refused.  This is the COFACTORLESS byte
+ * comparison that OpenSSL makes (not the cofactored equation [8][S]B = [8]R + [8][h]A that RFC 8032 also allows), so the verdict of
+ * every item is that of a one-by-one check: no random linear combination, no batch equation.
+ * status_in (optional): a lane whose word is not 0 does nothing and hands the word on, status_out[b] = status_in[b] - the pass chains
+ * with verify, weeding and the tallies in either order; none of that item's bytes are read.  status_out may be status_in itself.
+ *
+ * TIMING: variable time throughout.  The verifier sees public data only.  The SIGNER (eg_ed25519_keypair_*, eg_ed25519_sign_*) is a maker
+ * of test and benchmark items like the provers: its branches and table lookups depend on the secret scalar - it is not for a voter client.
+ * Ed25519 is deterministic, so the signer reproduces the bytes of any RFC 8032 signer (seed(32) -> SHA-512 -> clamp -> A = [a]B;
+ * r = SHA-512(hash prefix || M) mod l; R = [r]B; S = r + h a mod l).
+ *
+ * eg_ed25519_verify_device is asynchronous on `stream`, allocates nothing, never synchronises and takes no lock; `prefix` is HOST memory
+ * and is copied during the call; d_scratch holds eg_ed25519_verify_scratch_bytes(ctx, n) bytes (h of every item and the lanes' tables
+ * of -A, sized by the grid).  d_keys, d_sigs, d_key_index and the status arrays must be 4-byte aligned; the messages may lie anywhere.
+ * Refused with EG_ERR_BAD_ARG before anything is launched: NULL mandatory pointers with n > 0, prefix_len > 255, a NULL prefix with
+ * prefix_len > 0, msg_stride < msg_len, n >= 2^31, n_keys == 0 with n > 0, key_index == NULL with n_keys != n, a scratch that is too
+ * small.  n == 0 is EG_OK.  eg_ed25519_verify_batch: the same on host buffers, synchronous, with its own scratch. */
+enum { EG_ED25519_BAD_S = 1, EG_ED25519_BAD_KEY = 2, EG_ED25519_SMALL_ORDER = 3, EG_ED25519_MISMATCH = 4, EG_ED25519_BAD_INDEX = 5 };
+size_t eg_ed25519_verify_scratch_bytes(const eg_ctx*, size_t n);
+int eg_ed25519_verify_device(eg_ctx*, size_t n, const void* d_msgs, size_t msg_stride, size_t msg_len, const uint8_t* prefix /* host */,
+                             size_t prefix_len, const void* d_keys /* n_keys x 32 */, size_t n_keys,
+                             const void* d_key_index /* uint32[n] or NULL */, const void* d_sigs /* n x 64 */,
+                             const void* d_status_in /* uint32[n] or NULL */, void* d_status_out /* uint32[n] */, void* d_scratch,
+                             size_t scratch_bytes, void* stream);
+int eg_ed25519_verify_batch(eg_ctx*, size_t n, const uint8_t* msgs, size_t msg_stride, size_t msg_len, const uint8_t* prefix,
+                            size_t prefix_len, const uint8_t* keys /* n_keys x 32 */, size_t n_keys,
+                            const uint32_t* key_index /* n or NULL */, const uint8_t* sigs /* n x 64 */,
+                            const uint32_t* status_in /* n or NULL */, uint32_t* status_out /* n */);
+/* the signer (VARIABLE TIME, see TIMING): public keys of n seeds; signatures of n messages, item b under seeds[b].  The _device forms
+ * take device pointers (d_prefix too: prefix_len bytes in device memory, or NULL with prefix_len 0), are asynchronous on `stream` and
+ * take no lock; d_seeds anywhere, d_keys / d_sigs 4-byte aligned. */
+int eg_ed25519_keypair_batch(eg_ctx*, size_t n, const uint8_t* seeds /* n x 32 */, uint8_t* keys /* n x 32 */);
+int eg_ed25519_keypair_batch_device(eg_ctx*, size_t n, const void* d_seeds, void* d_keys, void* stream);
+int eg_ed25519_sign_batch(eg_ctx*, size_t n, const uint8_t* seeds /* n x 32 */, const uint8_t* msgs, size_t msg_stride, size_t msg_len,
+                          const uint8_t* prefix, size_t prefix_len, uint8_t* sigs /* n x 64 */);
+int eg_ed25519_sign_batch_device(eg_ctx*, size_t n, const void* d_seeds, const void* d_msgs, size_t msg_stride, size_t msg_len,
+                                 const void* d_prefix, size_t prefix_len, void* d_sigs, void* stream);
+/* SHA-512(prefix || msg_b) of n messages of one length, in the same prefix / stride form: the hash of the pass as a primitive */
+int eg_sha512_batch(eg_ctx*, size_t n, const uint8_t* msgs, size_t msg_stride, size_t msg_len, const uint8_t* prefix, size_t prefix_len,
+                    uint8_t* digests /* n x 64 */);
+int eg_sha512_batch_device(eg_ctx*, size_t n, const void* d_msgs, size_t msg_stride, size_t msg_len, const void* d_prefix,
+                           size_t prefix_len, void* d_digests /* n x 64, 4-byte aligned */, void* stream);
 
 /* ---- batch tier on several GPUs of ONE process (SURVEY.md 8b `device_mask`; the reference's host is one single-threaded process,
  * examples/voting.rs:179-213) -----------------------------------------------------------------------------------------------------

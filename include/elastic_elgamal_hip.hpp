@@ -745,6 +745,61 @@ struct Ristretto {
   Scalar scalar_neg(const Scalar& a) const { Scalar o; check(eg_scalar_neg_batch(ctx.raw(), 1, a.data(), o.data())); return o; }
 };
 
+// Voter signatures: Ed25519 (RFC 8032, pure EdDSA) of a batch in one pass (eg_hip.h, "voter signatures" has the rule).  Item b signs
+// prefix || msgs[b * stride, b * stride + msg_len) under keys[b], or under keys[key_index[b]] out of a roster; status = 0 or
+// EG_ST_BAD_SIGNATURE with the failed check (EG_ED25519_*) in EG_STATUS_DETAIL; a non-zero word of status_in is handed on.
+// The signer (keypairs, sign) is VARIABLE TIME: a maker of test and benchmark items, not for a voter client.
+struct Ed25519 {
+  const Context& ctx;
+  Bytes keypairs(const Bytes& seeds) const {
+    Bytes keys(seeds.size() / 32 * 32);
+    check(eg_ed25519_keypair_batch(ctx.raw(), seeds.size() / 32, seeds.data(), keys.data()));
+    return keys;
+  }
+  Bytes sign(const Bytes& seeds, const Bytes& msgs, size_t msg_len, const Bytes& prefix = Bytes(), size_t msg_stride = 0) const {
+    const size_t n = seeds.size() / 32;
+    Bytes sigs(n * 64);
+    check(eg_ed25519_sign_batch(ctx.raw(), n, seeds.data(), msgs.data(), msg_stride ? msg_stride : msg_len, msg_len, prefix.empty() ? nullptr : prefix.data(),
+                                prefix.size(), sigs.data()));
+    return sigs;
+  }
+  std::vector<uint32_t> verify(const Bytes& msgs, size_t msg_len, const Bytes& keys, const Bytes& sigs, const Bytes& prefix = Bytes(),
+                               const std::vector<uint32_t>& key_index = {}, const std::vector<uint32_t>& status_in = {}, size_t msg_stride = 0) const {
+    const size_t n = sigs.size() / 64;
+    if ((!key_index.empty() && key_index.size() != n) || (!status_in.empty() && status_in.size() != n)) throw Error(EG_ERR_BAD_ARG, "one key index / status word per item");
+    std::vector<uint32_t> status(n);
+    check(eg_ed25519_verify_batch(ctx.raw(), n, msgs.data(), msg_stride ? msg_stride : msg_len, msg_len, prefix.empty() ? nullptr : prefix.data(), prefix.size(),
+                                  keys.data(), keys.size() / 32, key_index.empty() ? nullptr : key_index.data(), sigs.data(),
+                                  status_in.empty() ? nullptr : status_in.data(), status.data()));
+    return status;
+  }
+  // asynchronous device-pointer form: d_scratch of verify_scratch_bytes(n) bytes; `prefix` is host memory; d_status_out may be d_status_in
+  size_t verify_scratch_bytes(size_t n) const { return eg_ed25519_verify_scratch_bytes(ctx.raw(), n); }
+  void verify_device(size_t n, const void* d_msgs, size_t msg_stride, size_t msg_len, const Bytes& prefix, const void* d_keys, size_t n_keys,
+                     const void* d_key_index, const void* d_sigs, const void* d_status_in, void* d_status_out, void* d_scratch, size_t scratch_bytes,
+                     void* stream = nullptr) const {
+    check(eg_ed25519_verify_device(ctx.raw(), n, d_msgs, msg_stride, msg_len, prefix.empty() ? nullptr : prefix.data(), prefix.size(), d_keys, n_keys,
+                                   d_key_index, d_sigs, d_status_in, d_status_out, d_scratch, scratch_bytes, stream));
+  }
+  void keypairs_device(size_t n, const void* d_seeds, void* d_keys, void* stream = nullptr) const {
+    check(eg_ed25519_keypair_batch_device(ctx.raw(), n, d_seeds, d_keys, stream));
+  }
+  void sign_device(size_t n, const void* d_seeds, const void* d_msgs, size_t msg_stride, size_t msg_len, const void* d_prefix, size_t prefix_len,
+                   void* d_sigs, void* stream = nullptr) const {
+    check(eg_ed25519_sign_batch_device(ctx.raw(), n, d_seeds, d_msgs, msg_stride, msg_len, d_prefix, prefix_len, d_sigs, stream));
+  }
+  // SHA-512(prefix || msg_b) of n messages of one length: 64 bytes each
+  Bytes sha512(size_t n, const Bytes& msgs, size_t msg_len, const Bytes& prefix = Bytes(), size_t msg_stride = 0) const {
+    Bytes out(n * 64);
+    check(eg_sha512_batch(ctx.raw(), n, msgs.data(), msg_stride ? msg_stride : msg_len, msg_len, prefix.empty() ? nullptr : prefix.data(), prefix.size(), out.data()));
+    return out;
+  }
+  void sha512_device(size_t n, const void* d_msgs, size_t msg_stride, size_t msg_len, const void* d_prefix, size_t prefix_len, void* d_digests,
+                     void* stream = nullptr) const {
+    check(eg_sha512_batch_device(ctx.raw(), n, d_msgs, msg_stride, msg_len, d_prefix, prefix_len, d_digests, stream));
+  }
+};
+
 // ---- tally stage (examples/voting.rs:122-177) ------------------------------------------------------------------------------------
 // Params::combine_shares (sharing/mod.rs:302-325): the first `threshold` of the given (participant index, dh element) pairs ->
 // the combined decryption [x]R, or nullopt when there are too few shares.  Verify the shares first (eg_share_params_create).
