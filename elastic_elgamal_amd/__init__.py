@@ -20,7 +20,7 @@ import os
 from pathlib import Path
 
 __all__ = [
-    "Context", "Ristretto", "Ed25519", "ChoiceParams", "QuadraticVotingParams", "PublicKeyVerifier", "DecryptionShareVerifier", "SumOfSquaresVerifier", "EgError", "library_path", "build",
+    "Context", "Ristretto", "Ed25519", "VoterRoll", "ChoiceParams", "QuadraticVotingParams", "PublicKeyVerifier", "DecryptionShareVerifier", "SumOfSquaresVerifier", "EgError", "library_path", "build",
     "STATUS_NAMES", "status_kind", "status_detail", "pack_json", "JsonPacker", "PACK_RESHAPE", "verify_json_multi", "json_stream_multi",
 ]
 
@@ -36,7 +36,7 @@ STATUS_NAMES = {
     5: "Range(LenMismatch)", 6: "Range(ChallengeMismatch)", 7: "Variant(LenMismatch)", 8: "Variant(ChallengeMismatch)",
     9: "CreditRange(LenMismatch)", 10: "CreditRange(ChallengeMismatch)", 11: "CreditEquivalence(LenMismatch)",
     12: "CreditEquivalence(ChallengeMismatch)", 13: "Malformed", 14: "Duplicate",
-    15: "BadSignature",
+    15: "BadSignature", 16: "Superseded",
 }
 
 
@@ -212,6 +212,11 @@ def _load() -> C.CDLL:
         "eg_ed25519_sign_batch_device": (C.c_int, [vp, sz, vp, vp, sz, sz, vp, sz, vp, vp]),
         "eg_sha512_batch": (C.c_int, [vp, sz, cp, sz, sz, cp, sz, cp]),
         "eg_sha512_batch_device": (C.c_int, [vp, sz, vp, sz, sz, vp, sz, vp, vp]),
+        "eg_roll_cast_scratch_bytes": (sz, [vp, sz, sz]),
+        "eg_roll_cast_device": (C.c_int, [vp, sz, vp, vp, C.c_uint64, C.c_int, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+        "eg_roll_cast": (C.c_int, [vp, sz, vp, vp, C.c_uint64, C.c_int, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "eg_roll_check_device": (C.c_int, [vp, sz, vp, vp, C.c_uint64, C.c_int, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "eg_roll_check": (C.c_int, [vp, sz, vp, vp, C.c_uint64, C.c_int, vp, sz, vp, vp, vp, vp, vp, vp, vp]),
         "eg_proof_params_create": (C.c_int, [vp, cp, C.c_int, C.c_uint64, C.POINTER(vp)]),
         "eg_share_params_create": (C.c_int, [vp, cp, C.c_uint64, C.c_uint64, C.c_uint64, cp, C.POINTER(vp)]),
         "eg_proof_params_destroy": (None, [vp]),
@@ -283,6 +288,11 @@ DUP_PRIOR = 0xFFFFFFFE           # include/eg_hip.h: EG_DUP_PRIOR, a ballot that
 WEED_KEYS_MAX = 1 << 30          # include/eg_hip.h: EG_WEED_KEYS_MAX
 ST_BAD_SIGNATURE = 15            # include/eg_hip.h: EG_ST_BAD_SIGNATURE, what Ed25519.verify writes; the detail is one of ED25519_*
 ED25519_BAD_S, ED25519_BAD_KEY, ED25519_SMALL_ORDER, ED25519_MISMATCH, ED25519_BAD_INDEX = 1, 2, 3, 4, 5
+ST_SUPERSEDED = 16               # include/eg_hip.h: EG_ST_SUPERSEDED, what VoterRoll writes into status_out; the detail is one of ROLL_*
+ROLL_FIRST, ROLL_LAST = 1, 2     # include/eg_hip.h: EG_ROLL_FIRST / EG_ROLL_LAST, the policy of a roll
+ROLL_SUPERSEDED, ROLL_OFF_ROLL, ROLL_NOT_CAST = 1, 2, 3
+SEQ_NONE = (1 << 64) - 1         # include/eg_hip.h: EG_SEQ_NONE
+ROLL_KEYS_MAX = 1 << 31          # include/eg_hip.h: EG_ROLL_KEYS_MAX
 
 
 def pack_json(text, n_options: int, single: bool | None = None, credits: int | None = None, threads: int = 0, max_objects: int = 0):
@@ -639,6 +649,98 @@ class Ed25519:
     def sha512_device(self, n: int, d_msgs: int, msg_stride: int, msg_len: int, d_digests: int, d_prefix: int = 0, prefix_len: int = 0, stream: int = 0):
         _check(_load().eg_sha512_batch_device(self.ctx._h, n, d_msgs or None, msg_stride, msg_len, d_prefix or None, prefix_len, d_digests or None,
                                               stream or None))
+
+
+class RollResult:
+    """What VoterRoll.cast / check say about a batch: per ballot superseded_by (SEQ_NONE: kept, not participating, or without a winner),
+    status_out, groups_out / weights_out (None without a roster array); displaced = [(old seq, new seq), ...] (cast only); found = the
+    three counters (superseded, displaced - check: not cast -, off the roll)."""
+
+    def __init__(self, superseded_by, status_out, groups_out, weights_out, displaced, found):
+        self.superseded_by, self.status_out, self.groups_out, self.weights_out = superseded_by, status_out, groups_out, weights_out
+        self.displaced, self.found = displaced, found
+
+    def kept(self, status_in=None):
+        """Indices of the ballots that count: they participate and their status word came through unchanged."""
+        return [b for b, s in enumerate(self.status_out) if s == 0 and (status_in is None or status_in[b] == 0)]
+
+
+class VoterRoll:
+    """One counted ballot per voter (include/eg_hip.h, "voter roll" has the rule): between weeding and the tally.  The roll is the caller's
+    list of n_keys 64-bit words (0 = no counted ballot yet), kept between calls; `policy` is ROLL_LAST or ROLL_FIRST and a roll belongs to
+    one policy.  Rolls of slabs, ranks or GPUs merge by the element-wise maximum (distributed.merge_rolls)."""
+
+    ST_SUPERSEDED, ROLL_FIRST, ROLL_LAST = ST_SUPERSEDED, ROLL_FIRST, ROLL_LAST
+    ROLL_SUPERSEDED, ROLL_OFF_ROLL, ROLL_NOT_CAST = ROLL_SUPERSEDED, ROLL_OFF_ROLL, ROLL_NOT_CAST
+    SEQ_NONE, ROLL_KEYS_MAX = SEQ_NONE, ROLL_KEYS_MAX
+
+    def __init__(self, ctx: Context, policy: int = ROLL_LAST):
+        self.ctx, self.policy = ctx, policy
+
+    def word(self, seq: int) -> int:
+        """EG_ROLL_WORD: the priority word of sequence number seq under this roll's policy."""
+        return seq + 1 if self.policy == ROLL_LAST else (1 << 63) - 1 - seq
+
+    def seq(self, word: int) -> int:
+        """EG_ROLL_SEQ: the sequence number behind a non-zero word."""
+        return word - 1 if self.policy == ROLL_LAST else (1 << 63) - 1 - word
+
+    def _host(self, cast: bool, key_index, roll, seq_base, status_in, roster_groups, roster_weights, want_displaced):
+        n, n_keys = len(key_index), len(roll)
+        idx = (C.c_uint32 * max(n, 1))(*key_index)
+        sin = (C.c_uint32 * max(n, 1))(*status_in) if status_in is not None else None
+        words = (C.c_uint64 * max(n_keys, 1))(*roll)
+        rg = (C.c_uint32 * max(n_keys, 1))(*roster_groups) if roster_groups is not None else None
+        rw = (C.c_uint64 * max(n_keys, 1))(*roster_weights) if roster_weights is not None else None
+        by, out = (C.c_uint64 * max(n, 1))(), (C.c_uint32 * max(n, 1))()
+        go = (C.c_uint32 * max(n, 1))() if rg is not None else None
+        wo = (C.c_uint64 * max(n, 1))() if rw is not None else None
+        found = (C.c_uint32 * 3)()
+        lib = _load()
+        if cast:
+            disp = (C.c_uint64 * max(2 * n, 1))() if want_displaced else None
+            count = C.c_uint64(0)
+            _check(lib.eg_roll_cast(self.ctx._h, n, idx, sin, seq_base, self.policy, words, n_keys, rg, rw, by, out, go, wo, disp,
+                                    C.byref(count) if want_displaced else None, found))
+            displaced = [(int(disp[2 * k]), int(disp[2 * k + 1])) for k in range(count.value)] if want_displaced else None
+        else:
+            _check(lib.eg_roll_check(self.ctx._h, n, idx, sin, seq_base, self.policy, words, n_keys, rg, rw, by, out, go, wo, found))
+            displaced = None
+        res = RollResult(list(by[:n]), list(out[:n]), list(go[:n]) if go is not None else None, list(wo[:n]) if wo is not None else None,
+                         displaced, list(found))
+        return res, list(words[:n_keys])
+
+    def cast(self, key_index, roll, seq_base: int = 0, status_in=None, roster_groups=None, roster_weights=None, displaced: bool = True):
+        """eg_roll_cast: (RollResult, the new roll).  key_index[b] = the roster index of the voter who signed ballot b, whose sequence
+        number is seq_base + b; a ballot participates iff its word of status_in is 0 (None: every ballot)."""
+        return self._host(True, key_index, roll, seq_base, status_in, roster_groups, roster_weights, displaced)
+
+    def check(self, key_index, roll, seq_base: int = 0, status_in=None, roster_groups=None, roster_weights=None) -> RollResult:
+        """eg_roll_check: the verdicts of a batch against a read-only roll (the final one, or a merged one)."""
+        return self._host(False, key_index, roll, seq_base, status_in, roster_groups, roster_weights, False)[0]
+
+    def cast_scratch_bytes(self, n: int, n_keys: int) -> int:
+        """Device scratch that cast_device needs (0 for arguments it refuses, and for n == 0)."""
+        return int(_load().eg_roll_cast_scratch_bytes(self.ctx._h, n, n_keys))
+
+    def cast_device(self, n: int, d_key_index: int, seq_base: int, d_roll: int, n_keys: int, d_superseded_by: int, d_found: int, d_scratch: int,
+                    scratch_bytes: int, d_status_in: int = 0, d_roster_groups: int = 0, d_roster_weights: int = 0, d_status_out: int = 0,
+                    d_groups_out: int = 0, d_weights_out: int = 0, d_displaced: int = 0, d_displaced_count: int = 0, stream: int = 0):
+        """Asynchronous device-pointer variant (eg_roll_cast_device): no allocation, no host synchronisation, no lock.  d_roll: n_keys uint64,
+        read and written; d_superseded_by: n uint64; d_found: 3 uint32; d_displaced: n x 2 uint64 with d_displaced_count (uint64), or both 0;
+        d_status_out may be d_status_in."""
+        _check(_load().eg_roll_cast_device(self.ctx._h, n, d_key_index or None, d_status_in or None, seq_base, self.policy, d_roll or None, n_keys,
+                                           d_roster_groups or None, d_roster_weights or None, d_superseded_by or None, d_status_out or None,
+                                           d_groups_out or None, d_weights_out or None, d_displaced or None, d_displaced_count or None,
+                                           d_found or None, d_scratch or None, scratch_bytes, stream or None))
+
+    def check_device(self, n: int, d_key_index: int, seq_base: int, d_roll: int, n_keys: int, d_superseded_by: int, d_found: int,
+                     d_status_in: int = 0, d_roster_groups: int = 0, d_roster_weights: int = 0, d_status_out: int = 0, d_groups_out: int = 0,
+                     d_weights_out: int = 0, stream: int = 0):
+        """Asynchronous device-pointer variant (eg_roll_check_device): the roll is only read."""
+        _check(_load().eg_roll_check_device(self.ctx._h, n, d_key_index or None, d_status_in or None, seq_base, self.policy, d_roll or None, n_keys,
+                                            d_roster_groups or None, d_roster_weights or None, d_superseded_by or None, d_status_out or None,
+                                            d_groups_out or None, d_weights_out or None, d_found or None, stream or None))
 
 
 def prepared_point_size() -> int:

@@ -35,6 +35,7 @@
 #include "share_combine_kernels.cuh"
 #include "weed_kernels.cuh"
 #include "ed25519_kernels.cuh"
+#include "roll_kernels.cuh"
 
 using namespace eg;
 
@@ -4085,6 +4086,7 @@ int eg_ed25519_verify_device(eg_ctx* c, size_t n, const void* d_msgs, size_t msg
 struct EdStage {
   std::vector<void*> bufs;
   hipStream_t s = nullptr;
+  const char* who = "ed25519";
   ~EdStage() {
     for (void* p : bufs) if (p) (void)hipFree(p);
     if (s) (void)hipStreamDestroy(s);
@@ -4093,7 +4095,7 @@ struct EdStage {
   int put(void** out, const void* src, size_t bytes) {        // src null: room only
     void* p = nullptr;
     const hipError_t he = hipMalloc(&p, std::max<size_t>(bytes, 16));
-    if (he == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(EG_ERR_NOMEM, "ed25519: the staging buffers do not fit the device memory"); }
+    if (he == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(EG_ERR_NOMEM, std::string(who) + ": the staging buffers do not fit the device memory"); }
     HIPCHK(he);
     bufs.push_back(p);
     if (src && bytes) HIPCHK(hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, s));
@@ -4205,6 +4207,159 @@ int eg_sha512_batch(eg_ctx* c, size_t n, const uint8_t* msgs, size_t msg_stride,
   HIPCHK(hipMemcpyAsync(digests, dd, n * 64, hipMemcpyDeviceToHost, st.s));
   HIPCHK(hipStreamSynchronize(st.s));
   return EG_OK;
+}
+
+// ---- voter roll: the one ballot of every voter that counts (roll_kernels.cuh; the rule: include/eg_hip.h) -------------------------------
+// Stateless like weeding and the signature pass: everything is the caller's - no lock, no workspace of the context.
+// The argument rules come first and need no context (so they can be tested without a GPU); what passes them fails on a null context.
+static int roll_check_args(size_t n, size_t n_keys, uint64_t seq_base, int policy, const egr::Have& h) {
+  if (const char* why = egr::refuse(n, n_keys, seq_base, policy, h)) return fail(EG_ERR_BAD_ARG, std::string("roll: ") + why);
+  return EG_OK;
+}
+static int roll_check_ctx(const eg_ctx* c) { return c ? EG_OK : fail(EG_ERR_BAD_ARG, "roll: null ctx"); }
+static int roll_check_aligned(uintptr_t words64, uintptr_t words32) {
+  if (words64 & 7u) return fail(EG_ERR_BAD_ARG, "roll: roll, roster_weights, superseded_by, weights_out, displaced and displaced_count must be 8-byte aligned");
+  if (words32 & 3u) return fail(EG_ERR_BAD_ARG, "roll: key_index, the status arrays, roster_groups, groups_out, found and scratch must be 4-byte aligned");
+  return EG_OK;
+}
+size_t eg_roll_cast_scratch_bytes(const eg_ctx* c, size_t n, size_t n_keys) {
+  return c && !egr::refuse_sizes(n, n_keys) ? egr::layout(n, n_keys).total : 0;
+}
+int eg_roll_cast_device(eg_ctx* c, size_t n, const void* d_key_index, const void* d_status_in, uint64_t seq_base, int policy, void* d_roll,
+                        size_t n_keys, const void* d_roster_groups, const void* d_roster_weights, void* d_superseded_by, void* d_status_out,
+                        void* d_groups_out, void* d_weights_out, void* d_displaced, void* d_displaced_count, void* d_found, void* d_scratch,
+                        size_t scratch_bytes, void* stream) {
+  TRY_(roll_check_args(n, n_keys, seq_base, policy,
+                       egr::Have{d_key_index != nullptr, d_roll != nullptr, d_superseded_by != nullptr, d_found != nullptr, d_roster_groups != nullptr,
+                                 d_roster_weights != nullptr, d_groups_out != nullptr, d_weights_out != nullptr, d_displaced != nullptr,
+                                 d_displaced_count != nullptr}));
+  TRY_(roll_check_aligned((uintptr_t)d_roll | (uintptr_t)d_roster_weights | (uintptr_t)d_superseded_by | (uintptr_t)d_weights_out |
+                              (uintptr_t)d_displaced | (uintptr_t)d_displaced_count,
+                          (uintptr_t)d_key_index | (uintptr_t)d_status_in | (uintptr_t)d_status_out | (uintptr_t)d_roster_groups |
+                              (uintptr_t)d_groups_out | (uintptr_t)d_found | (uintptr_t)d_scratch));
+  const egr::Layout L = egr::layout(n, n_keys);
+  if (L.total && (!d_scratch || scratch_bytes < L.total))
+    return fail(EG_ERR_BAD_ARG, "roll: scratch is null or too small (eg_roll_cast_scratch_bytes says how much)");
+  TRY_(roll_check_ctx(c));
+  if (!d_found && !d_displaced_count) return EG_OK;                       // n == 0 and nowhere to write anything to
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)stream;
+  u32* found = static_cast<u32*>(d_found);
+  if (found) HIPCHK(hipMemsetAsync(found, 0, 3 * sizeof(u32), s));
+  if (n == 0) {
+    if (d_displaced_count) HIPCHK(hipMemsetAsync(d_displaced_count, 0, sizeof(uint64_t), s));
+    return EG_OK;
+  }
+  char* base = static_cast<char*>(d_scratch);
+  u32* best = reinterpret_cast<u32*>(base + L.best);
+  u32* flag = reinterpret_cast<u32*>(base + L.flag);
+  u32* tiles = reinterpret_cast<u32*>(base + L.tiles);
+  const u32* status = static_cast<const u32*>(d_status_in);
+  const RollMemDev mem{static_cast<const u32*>(d_key_index), best, static_cast<unsigned long long*>(d_roll), static_cast<const u32*>(d_roster_groups),
+                       static_cast<const unsigned long long*>(d_roster_weights), static_cast<unsigned long long*>(d_displaced)};
+  const RollOutDev out{static_cast<unsigned long long*>(d_superseded_by), static_cast<u32*>(d_status_out), static_cast<u32*>(d_groups_out),
+                       static_cast<unsigned long long*>(d_weights_out)};
+  const unsigned blocks = (unsigned)((n + ROLL_NT - 1) / ROLL_NT);
+  HIPCHK(hipMemsetAsync(best, 0, n_keys * sizeof(u32), s));
+  hipLaunchKernelGGL(k_roll_claim, dim3(blocks), dim3(ROLL_NT), 0, s, mem, status, (uint64_t)n, policy, (uint64_t)n_keys);
+  hipLaunchKernelGGL(k_roll_resolve, dim3(blocks), dim3(ROLL_NT), 0, s, mem, status, (uint64_t)n, seq_base, policy, (uint64_t)n_keys, out, flag, found);
+  if (d_displaced) {
+    hipLaunchKernelGGL(k_roll_scan_tiles, dim3(L.n_tiles), dim3(ROLL_NT), 0, s, (const u32*)flag, (u32)n, tiles);
+    hipLaunchKernelGGL(k_roll_scan_tops, dim3(1), dim3(64), 0, s, L.n_tiles, tiles, static_cast<unsigned long long*>(d_displaced_count));
+    hipLaunchKernelGGL(k_roll_scan_apply, dim3(L.n_tiles), dim3(ROLL_NT), 0, s, flag, (u32)n, (const u32*)tiles);
+  }
+  hipLaunchKernelGGL(k_roll_commit, dim3(blocks), dim3(ROLL_NT), 0, s, mem, (const u32*)flag, (uint64_t)n, seq_base, policy, (uint64_t)n_keys);
+  HIPCHK(hipGetLastError());
+  return EG_OK;
+}
+int eg_roll_check_device(eg_ctx* c, size_t n, const void* d_key_index, const void* d_status_in, uint64_t seq_base, int policy, const void* d_roll,
+                         size_t n_keys, const void* d_roster_groups, const void* d_roster_weights, void* d_superseded_by, void* d_status_out,
+                         void* d_groups_out, void* d_weights_out, void* d_found, void* stream) {
+  TRY_(roll_check_args(n, n_keys, seq_base, policy,
+                       egr::Have{d_key_index != nullptr, d_roll != nullptr, d_superseded_by != nullptr, d_found != nullptr, d_roster_groups != nullptr,
+                                 d_roster_weights != nullptr, d_groups_out != nullptr, d_weights_out != nullptr, false, false}));
+  TRY_(roll_check_aligned((uintptr_t)d_roll | (uintptr_t)d_roster_weights | (uintptr_t)d_superseded_by | (uintptr_t)d_weights_out,
+                          (uintptr_t)d_key_index | (uintptr_t)d_status_in | (uintptr_t)d_status_out | (uintptr_t)d_roster_groups |
+                              (uintptr_t)d_groups_out | (uintptr_t)d_found));
+  TRY_(roll_check_ctx(c));
+  if (!d_found) return EG_OK;                                             // n == 0 and nowhere to write anything to
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)stream;
+  u32* found = static_cast<u32*>(d_found);
+  HIPCHK(hipMemsetAsync(found, 0, 3 * sizeof(u32), s));
+  if (n == 0) return EG_OK;
+  // the roll is only read: the lane function has no store, the cast away of const serves the shared view of the memory
+  const RollMemDev mem{static_cast<const u32*>(d_key_index), nullptr, static_cast<unsigned long long*>(const_cast<void*>(d_roll)),
+                       static_cast<const u32*>(d_roster_groups), static_cast<const unsigned long long*>(d_roster_weights), nullptr};
+  const RollOutDev out{static_cast<unsigned long long*>(d_superseded_by), static_cast<u32*>(d_status_out), static_cast<u32*>(d_groups_out),
+                       static_cast<unsigned long long*>(d_weights_out)};
+  hipLaunchKernelGGL(k_roll_check, dim3((unsigned)((n + ROLL_NT - 1) / ROLL_NT)), dim3(ROLL_NT), 0, s, mem, static_cast<const u32*>(d_status_in),
+                     (uint64_t)n, seq_base, policy, (uint64_t)n_keys, out, found);
+  HIPCHK(hipGetLastError());
+  return EG_OK;
+}
+// host arrays, staged on a stream of the call's own; `cast`: the roll comes back, with the displaced entries
+static int roll_host(eg_ctx* c, bool cast, size_t n, const uint32_t* key_index, const uint32_t* status_in, uint64_t seq_base, int policy,
+                     const uint64_t* roll, uint64_t* roll_out, size_t n_keys, const uint32_t* roster_groups, const uint64_t* roster_weights,
+                     uint64_t* superseded_by, uint32_t* status_out, uint32_t* groups_out, uint64_t* weights_out, uint64_t* displaced,
+                     uint64_t* displaced_count, uint32_t* found) {
+  TRY_(roll_check_args(n, n_keys, seq_base, policy,
+                       egr::Have{key_index != nullptr, roll != nullptr, superseded_by != nullptr, found != nullptr, roster_groups != nullptr,
+                                 roster_weights != nullptr, groups_out != nullptr, weights_out != nullptr, displaced != nullptr,
+                                 displaced_count != nullptr}));
+  TRY_(roll_check_ctx(c));
+  if (found) found[0] = found[1] = found[2] = 0;
+  if (displaced_count) *displaced_count = 0;
+  if (n == 0) return EG_OK;
+  HIPCHK(hipSetDevice(c->device));
+  EdStage st; st.who = "roll"; TRY_(st.open());
+  const size_t need = cast ? eg_roll_cast_scratch_bytes(c, n, n_keys) : 0;
+  void *di, *dsi = nullptr, *dr, *dg = nullptr, *dw = nullptr, *dby, *dso = nullptr, *dgo = nullptr, *dwo = nullptr, *dd = nullptr, *dtail, *scratch = nullptr;
+  TRY_(st.put(&di, key_index, n * 4));
+  if (status_in) TRY_(st.put(&dsi, status_in, n * 4));
+  TRY_(st.put(&dr, roll, n_keys * 8));
+  if (roster_groups) TRY_(st.put(&dg, roster_groups, n_keys * 4));
+  if (roster_weights) TRY_(st.put(&dw, roster_weights, n_keys * 8));
+  TRY_(st.put(&dby, nullptr, n * 8));
+  if (status_out) TRY_(st.put(&dso, nullptr, n * 4));
+  if (groups_out) TRY_(st.put(&dgo, nullptr, n * 4));
+  if (weights_out) TRY_(st.put(&dwo, nullptr, n * 8));
+  if (displaced) TRY_(st.put(&dd, nullptr, n * 16));
+  TRY_(st.put(&dtail, nullptr, 32));                                      // the displaced count (uint64), then the three counters
+  if (cast) TRY_(st.put(&scratch, nullptr, need));
+  void* d_count = displaced ? dtail : nullptr;
+  void* d_found = static_cast<char*>(dtail) + 8;
+  if (cast)
+    TRY_(eg_roll_cast_device(c, n, di, dsi, seq_base, policy, dr, n_keys, dg, dw, dby, dso, dgo, dwo, dd, d_count, d_found, scratch, need, st.s));
+  else
+    TRY_(eg_roll_check_device(c, n, di, dsi, seq_base, policy, dr, n_keys, dg, dw, dby, dso, dgo, dwo, d_found, st.s));
+  unsigned long long count = 0;
+  HIPCHK(hipMemcpyAsync(superseded_by, dby, n * 8, hipMemcpyDeviceToHost, st.s));
+  if (status_out) HIPCHK(hipMemcpyAsync(status_out, dso, n * 4, hipMemcpyDeviceToHost, st.s));
+  if (groups_out) HIPCHK(hipMemcpyAsync(groups_out, dgo, n * 4, hipMemcpyDeviceToHost, st.s));
+  if (weights_out) HIPCHK(hipMemcpyAsync(weights_out, dwo, n * 8, hipMemcpyDeviceToHost, st.s));
+  if (cast) HIPCHK(hipMemcpyAsync(roll_out, dr, n_keys * 8, hipMemcpyDeviceToHost, st.s));
+  HIPCHK(hipMemcpyAsync(found, d_found, 3 * sizeof(u32), hipMemcpyDeviceToHost, st.s));
+  if (displaced) HIPCHK(hipMemcpyAsync(&count, d_count, sizeof count, hipMemcpyDeviceToHost, st.s));
+  HIPCHK(hipStreamSynchronize(st.s));
+  if (displaced && count && count <= n) {
+    HIPCHK(hipMemcpyAsync(displaced, dd, (size_t)count * 16, hipMemcpyDeviceToHost, st.s));
+    HIPCHK(hipStreamSynchronize(st.s));
+  }
+  if (displaced_count) *displaced_count = count;
+  return EG_OK;
+}
+int eg_roll_cast(eg_ctx* c, size_t n, const uint32_t* key_index, const uint32_t* status_in, uint64_t seq_base, int policy, uint64_t* roll,
+                 size_t n_keys, const uint32_t* roster_groups, const uint64_t* roster_weights, uint64_t* superseded_by, uint32_t* status_out,
+                 uint32_t* groups_out, uint64_t* weights_out, uint64_t* displaced, uint64_t* displaced_count, uint32_t* found) {
+  return roll_host(c, true, n, key_index, status_in, seq_base, policy, roll, roll, n_keys, roster_groups, roster_weights, superseded_by, status_out,
+                   groups_out, weights_out, displaced, displaced_count, found);
+}
+int eg_roll_check(eg_ctx* c, size_t n, const uint32_t* key_index, const uint32_t* status_in, uint64_t seq_base, int policy, const uint64_t* roll,
+                  size_t n_keys, const uint32_t* roster_groups, const uint64_t* roster_weights, uint64_t* superseded_by, uint32_t* status_out,
+                  uint32_t* groups_out, uint64_t* weights_out, uint32_t* found) {
+  return roll_host(c, false, n, key_index, status_in, seq_base, policy, roll, nullptr, n_keys, roster_groups, roster_weights, superseded_by,
+                   status_out, groups_out, weights_out, nullptr, nullptr, found);
 }
 
 }  // extern "C"

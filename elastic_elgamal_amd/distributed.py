@@ -69,3 +69,20 @@ def gather_rows(row, device) -> list[list[float]]:
     parts = [torch.empty_like(t) for _ in range(dist.get_world_size())]
     dist.all_gather(parts, t)
     return [p.cpu().tolist() for p in parts]
+
+
+def merge_rolls(local_roll: torch.Tensor) -> torch.Tensor:
+    """Voter rolls of the ranks -> the merged roll, on every rank: ONE all-reduce with MAX over the words viewed as int64 (valid because
+    every word is below 2^63, include/eg_hip.h "voter roll").  local_roll: int64 or uint64 [n_keys], one roll per rank under one policy,
+    cast with global sequence numbers.  Every rank then re-judges its slabs with VoterRoll.check against the result.  A single process
+    returns its input."""
+    if _single():
+        return local_roll
+    words = local_roll.contiguous().view(torch.int64).clone()
+    if dist.get_backend() == "gloo":      # CPU tests, and a one-GPU rehearsal of N > 1: gloo reduces host tensors
+        host = words.cpu()
+        dist.all_reduce(host, op=dist.ReduceOp.MAX)
+        words = host.to(local_roll.device)
+    else:
+        dist.all_reduce(words, op=dist.ReduceOp.MAX)
+    return words.view(local_roll.dtype)

@@ -1,7 +1,7 @@
 // voting.cpp -- the reference's examples/voting.rs on the GPU backend, in C++ on top of the C ABI:
 //   `Args::vote`            (examples/voting.rs:179-213)  ./voting [votes] [options] [seed]
 //   `Args::quadratic_vote`  (examples/voting.rs:219-269)  ./voting --qv [votes] [options] [credits] [seed]
-//   options: --devices N, --json, --precincts P, --weighted, --replays K, --signed K
+//   options: --devices N, --json, --precincts P, --weighted, --replays K, --signed K, --revotes K
 // talliers' key -> voters create ballots from their own choices -> verify every ballot -> homomorphic totals -> decrypt and
 // compare with the EXPECTED totals the voters' choices add up to.  Threshold sharing of the key (examples/voting.rs:105-120) is out
 // of scope; a single key pair stands in for the shared key (tests/test_gpu_parity.py::test_threshold_tally_end_to_end
@@ -21,6 +21,11 @@
 // envelopes are forged: a right signature under another voter's roster index, or a flipped bit.  The signature pass (Ed25519::verify =
 // eg_ed25519_verify_batch) runs before the ballots are verified; its status words are chained with the verifier's, and the K forgeries,
 // and only they, are left out of the tally (tally_grouped over the chained words) - their ballots themselves are perfectly valid.
+// With --revotes K (choice ballots), K voters cast a second ballot with another choice.  Both ballots are fresh and valid, so neither
+// verification nor weeding objects; the voter-roll pass (VoterRoll::cast = eg_roll_cast, policy EG_ROLL_LAST: the last ballot of a
+// voter counts) runs between weeding and the tally, reports the K first ballots as superseded and hands the voters' precincts and
+// weights to the tally from the roster (groups_out / weights_out: --precincts and --weighted combine with it); the decrypted totals
+// must equal those of the last ballots.
 //
 //   g++ -std=c++17 -Iinclude examples/voting.cpp -Lelastic_elgamal_amd -leg_hip -Wl,-rpath,$PWD/elastic_elgamal_amd -o voting
 #include <cstdio>
@@ -149,6 +154,67 @@ static bool replayed_tally(const Context& ctx, const Ristretto& group, const Sca
   return ok;
 }
 
+// --revotes: K voters cast a second ballot with another choice; verify, weed, roll (the last ballot counts), tally with the roster's
+// precincts and weights - the totals of the last ballots
+static bool revoted_tally(const Context& ctx, const Ristretto& group, const Scalar& sk, const ChoiceParams& params, const Bytes& ballots,
+                          const std::vector<size_t>& choices, size_t revotes, size_t options, uint32_t precincts, bool weighted, uint64_t seed) {
+  const size_t votes = choices.size(), n = votes + revotes;
+  std::vector<uint32_t> voter(n);
+  std::vector<size_t> cast_choice = choices, again(revotes);
+  for (size_t v = 0; v < votes; ++v) voter[v] = (uint32_t)v;
+  for (size_t i = 0; i < revotes; ++i) {
+    voter[votes + i] = (uint32_t)((7 * i) % votes);
+    again[i] = (choices[voter[votes + i]] + 1) % options;
+    cast_choice.push_back(again[i]);
+  }
+  Bytes all = ballots;
+  const Bytes second = params.encrypt_single_choices(seed ^ 0x5ec0ull, votes, again);
+  all.insert(all.end(), second.begin(), second.end());
+  const auto verdict = params.verify_batch(all);
+  printf("with %zu re-votes: %zu of %zu ballots verified\n", revotes, verdict.accepted(), n);
+  std::vector<uint32_t> status(n);
+  for (size_t b = 0; b < n; ++b) status[b] = verdict.results[b] ? 1u : 0u;
+  const Weeded w = params.weed(all, status);                       // a superseded ballot's ciphertexts still belong on the board
+  // the roster: voter v's precinct and weight, whatever the ballots say
+  const uint32_t n_groups = precincts ? precincts : 1u;
+  std::vector<uint32_t> roster_groups(votes);
+  std::vector<uint64_t> roster_weights(votes), words(votes, 0);
+  for (size_t v = 0; v < votes; ++v) { roster_groups[v] = (uint32_t)(v % n_groups); roster_weights[v] = weighted ? weight_of(v) : 1; }
+  const VoterRoll roll{ctx, EG_ROLL_LAST};
+  const RollVerdicts r = roll.cast(voter, words, 0, w.status, roster_groups, roster_weights);
+  for (size_t b = 0; b < n; ++b)
+    if (r.superseded_by[b] != EG_SEQ_NONE) printf("  ballot #%zu superseded by ballot #%llu\n", b + 1, (unsigned long long)r.superseded_by[b] + 1);
+  printf("the roll superseded %u ballots\n", r.found[0]);
+  // what the last accepted ballot of every voter adds up to, per precinct
+  std::vector<std::vector<uint64_t>> expected(n_groups, std::vector<uint64_t>(options, 0));
+  std::vector<uint64_t> weight_sum(n_groups, 0);
+  std::vector<long> last(votes, -1);
+  size_t superseded = 0;
+  for (size_t b = 0; b < n; ++b) if (!w.status[b]) { superseded += last[voter[b]] >= 0; last[voter[b]] = (long)b; }
+  for (size_t v = 0; v < votes; ++v) {
+    if (last[v] < 0) continue;
+    expected[roster_groups[v]][cast_choice[(size_t)last[v]]] += roster_weights[v];
+    weight_sum[roster_groups[v]] += roster_weights[v];
+  }
+  const WeightedTally t = params.tally_weighted(all, r.status_out, r.weights_out, 16, r.groups_out, n_groups);
+  bool ok = r.found[0] == superseded && r.found[2] == 0 && r.displaced.empty();
+  const DiscreteLogSolver solver(ctx);
+  for (uint32_t g = 0; g < n_groups; ++g) {
+    std::vector<Element> decrypted;
+    for (const Ciphertext& c : t.totals[g]) decrypted.push_back(group.sub(c.blinded_element, group.mul(c.random_element, sk)));
+    const std::vector<std::optional<uint64_t>> found = solver.solve(decrypted, 0, weight_sum[g]);
+    ok = ok && t.weight_sums[g].low == weight_sum[g] && !t.weight_sums[g].high;
+    for (size_t k = 0; k < options; ++k) {
+      if (precincts) printf("  precinct #%u", g + 1);
+      printf("  variant #%zu total after the roll: %llu (expected %llu)\n", k + 1, found[k] ? (unsigned long long)*found[k] : 0ull,
+             (unsigned long long)expected[g][k]);
+      ok = ok && found[k] && *found[k] == expected[g][k];
+    }
+  }
+  printf("the totals %s those of the last ballots\n", ok ? "equal" : "DIFFER from");
+  return ok;
+}
+
 // --signed: every voter signs the packed ballot under a roster key; K envelopes are forged; signature pass -> verify -> tally of the rest
 template <class Params>
 static bool signed_tally(const Context& ctx, const Ristretto& group, const Scalar& sk, const Params& params, const Bytes& ballots, size_t votes,
@@ -223,7 +289,7 @@ static std::string choice_to_json(const uint8_t* b, size_t options) {
 int main(int argc, char** argv) {
   bool qv = false, json = false, weighted = false;
   int devices = 1;
-  long precincts = 0, replays = 0, signed_forgeries = -1;
+  long precincts = 0, replays = 0, signed_forgeries = -1, revotes = 0;
   std::vector<std::string> pos;
   for (int i = 1; i < argc; ++i) {
     if (!strcmp(argv[i], "--qv")) qv = true;
@@ -233,6 +299,7 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "--precincts") && i + 1 < argc) precincts = atol(argv[++i]);
     else if (!strcmp(argv[i], "--replays") && i + 1 < argc) replays = atol(argv[++i]);
     else if (!strcmp(argv[i], "--signed") && i + 1 < argc) signed_forgeries = atol(argv[++i]);
+    else if (!strcmp(argv[i], "--revotes") && i + 1 < argc) revotes = atol(argv[++i]);
     else pos.push_back(argv[i]);
   }
   auto arg = [&](size_t k, uint64_t dflt) { return k < pos.size() ? strtoull(pos[k].c_str(), nullptr, 10) : dflt; };
@@ -242,6 +309,9 @@ int main(int argc, char** argv) {
   if (replays < 0 || replays > 1000000 || (replays && !votes)) { printf("--replays must be in 0..1000000 and needs a voter to copy\n"); return 2; }
   if (signed_forgeries < -1 || (signed_forgeries >= 0 && (size_t)signed_forgeries > votes) || (signed_forgeries > 0 && votes < 2)) {
     printf("--signed K needs 0 <= K <= votes and two voters to forge\n"); return 2;
+  }
+  if (revotes < 0 || (revotes && (qv || options < 2 || (size_t)revotes * 7 > votes))) {
+    printf("--revotes K is shown for choice ballots with two options or more and needs 7 K <= votes\n"); return 2;
   }
   if (precincts < 0 || precincts > (long)EG_TALLY_GROUPS_MAX) { printf("--precincts must be in 0..%u\n", EG_TALLY_GROUPS_MAX); return 2; }
 
@@ -311,6 +381,7 @@ int main(int argc, char** argv) {
       ok = signed_tally(ctx, group, sk, *params[0], ballots, votes, (size_t)signed_forgeries, one_hot, options, votes, seed) && ok;
     }
     if (replays) ok = replayed_tally(ctx, group, sk, *params[0], ballots, votes, (size_t)replays, expected, votes) && ok;
+    if (revotes) ok = revoted_tally(ctx, group, sk, *params[0], ballots, choices, (size_t)revotes, options, (uint32_t)precincts, weighted, seed) && ok;
   } else {
     std::vector<std::unique_ptr<QuadraticVotingParams>> params;
     for (auto& c : ctxs) params.push_back(std::make_unique<QuadraticVotingParams>(*c, pk, options, credits));

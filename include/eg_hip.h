@@ -113,8 +113,10 @@ enum {
                                      responses, wrong proof kind: serde.rs:29-80,303-355); object-ingest layer only */
   EG_ST_DUPLICATE = 14,           /* no verdict of the reference: an accepted ballot that repeats a tally ciphertext of the board or of an
                                      earlier ballot; written by eg_*_weed* into status_out only, detail 0 */
-  EG_ST_BAD_SIGNATURE = 15        /* no verdict of the reference: the voter's Ed25519 signature over the item does not hold; written by
+  EG_ST_BAD_SIGNATURE = 15,       /* no verdict of the reference: the voter's Ed25519 signature over the item does not hold; written by
                                      eg_ed25519_verify* only, detail = which check failed (EG_ED25519_*) */
+  EG_ST_SUPERSEDED = 16           /* no verdict of the reference: not the one ballot of its voter that counts; written by eg_roll_* into
+                                     status_out only, detail = why (EG_ROLL_SUPERSEDED / _OFF_ROLL / _NOT_CAST) */
 };
 #define EG_STATUS_KIND(s) ((s) & 0xffu)
 #define EG_STATUS_DETAIL(s) ((s) >> 8)
@@ -547,6 +549,93 @@ int eg_sha512_batch(eg_ctx*, size_t n, const uint8_t* msgs, size_t msg_stride, s
                     uint8_t* digests /* n x 64 */);
 int eg_sha512_batch_device(eg_ctx*, size_t n, const void* d_msgs, size_t msg_stride, size_t msg_len, const void* d_prefix,
                            size_t prefix_len, void* d_digests /* n x 64, 4-byte aligned */, void* stream);
+
+/* ---- voter roll: one counted ballot per voter, by a policy, across batches and GPUs ----------------------------------------------------
+ * Weeding flags a byte-for-byte copy and the signature pass a ballot that is not signed under a registered key; neither limits how many
+ * fresh, validly signed ballots ONE registered voter gets counted.  Systems that allow re-voting as a defence against coercion count one
+ * of them (Helios, Estonia: the last).  This pass says, per ballot, whether it is the one ballot of its voter that counts, and hands the
+ * voter's precinct and weight to the tally FROM THE ROSTER, so that a voter cannot choose either by sending other arrays.
+ * ORDER IN THE CHAIN: signatures -> verify -> weed -> roll -> tally.  A superseded ballot's ciphertexts are public, so they still belong
+ * on the weeding board (weed first, over every accepted ballot); a weeded copy must not claim its voter's slot (roll after weeding, over
+ * weeding's status_out).
+ *
+ * INPUTS.  key_index[b] (uint32) = the roster index of the voter who signed ballot b: the array the signature pass takes.  Ballot b has
+ * the global SEQUENCE NUMBER s_b = seq_base + b; seq_base is the caller's count of ballots before this batch.  Ballot b PARTICIPATES iff
+ * status_in == NULL or status_in[b] == EG_ST_OK; nothing else of a ballot that does not participate is read.
+ * THE ROLL is the caller's array of n_keys uint64 words, zero-initialised, kept between calls, one word per roster key.  0 = no counted
+ * ballot yet; otherwise the word is a PRIORITY that encodes the sequence number s of the counted ballot:
+ *   EG_ROLL_LAST   word = s + 1             (the last ballot of a voter counts)
+ *   EG_ROLL_FIRST  word = 2^63 - 1 - s      (the first one does)
+ * s <= 2^63 - 2, so every word is in [1, 2^63 - 1] and signed and unsigned order agree.  Under either policy THE LARGER WORD WINS.  A roll
+ * belongs to one policy.  EG_ROLL_WORD(seq, policy) / EG_ROLL_SEQ(word, policy) convert.
+ * CAST.  For a voter v let C_v be the old roll[v] (if non-zero) together with the words of the participating ballots with key_index[b]
+ * == v.  The new roll[v] = max C_v; voters without a ballot in the batch are not touched.  Ballot b is KEPT iff it participates,
+ * key_index[b] < n_keys and its word equals the new roll[v].  The rule is a maximum, hence commutative and idempotent: batches may be
+ * cast in any order, casting a batch twice changes nothing, and rolls of slabs, ranks or GPUs MERGE by the element-wise maximum of the
+ * 64-bit words (as int64 or uint64: the words are below 2^63).
+ * OUTPUTS per ballot.  superseded_by[b] (uint64) = EG_SEQ_NONE for a kept ballot, one that does not participate, and one without a winner
+ * (off the roll, not cast); otherwise the sequence number decoded from the winning word.  status_out[b] (optional, may be status_in
+ * itself) = status_in[b] (0 without one) for kept ballots and those that do not participate, otherwise EG_ST_SUPERSEDED with the detail
+ *   EG_ROLL_SUPERSEDED 1  another ballot of the voter wins
+ *   EG_ROLL_OFF_ROLL   2  key_index[b] >= n_keys; the value is never used as an index.  The signature pass refuses it already, so it
+ *                         appears only with forged or skipped status words
+ *   EG_ROLL_NOT_CAST   3  the check entries only: roll[v] == 0
+ * groups_out[b] (optional, needs roster_groups[n_keys], uint32) = roster_groups[v] for a kept ballot, EG_GROUP_NONE otherwise;
+ * weights_out[b] (optional, needs roster_weights[n_keys], uint64) = the roster weight for a kept ballot, 0 otherwise: exactly the arrays
+ * eg_*_tally_grouped / _weighted take, beside status_out.
+ * DISPLACED (optional, room for n entries of two uint64; comes with displaced_count).  For every voter whose NON-ZERO old word was
+ * replaced in this call one entry (old sequence number, new sequence number), in ascending order of the winning ballot's index b;
+ * *displaced_count (uint64) = their number.  It tells a host that keeps an archive or running tallies which earlier ballots have just
+ * stopped counting.
+ * FOUND.  The library WRITES three uint32 words: found[0] = participating ballots superseded (detail 1), found[1] = displaced entries
+ * (counted with or without the array), found[2] = participating ballots off the roll.
+ * CHECK.  eg_roll_check* takes the same inputs against a READ-ONLY roll - the final one at the close of the election, or a merged one.
+ * Ballot b is kept iff it participates, its index is in range and roll[v] == EG_ROLL_WORD(s_b, policy).  The outputs are the same
+ * without `displaced`; found[1] counts EG_ROLL_NOT_CAST.  It lets every archived batch be re-judged against the final roll before the
+ * tally, and it is the second half of the MULTI-GPU RECIPE: every rank casts its slabs into a roll of its own (global sequence numbers),
+ * the rolls are merged by one element-wise maximum (an all-reduce with MAX over int64), and every rank checks its slabs against the
+ * merged roll.  The kept set is that of one cast over the concatenation.
+ *
+ * STATELESS with respect to the engine, as weeding and the signature pass: device pointers and a stream, no lock, no workspace of the
+ * context; the verdict is a pure function of the inputs and does not depend on the order in which lanes run.  The `_device` forms are
+ * asynchronous on `stream`, allocate nothing and never synchronise.  d_scratch of a cast holds eg_roll_cast_scratch_bytes(ctx, n, n_keys)
+ * bytes (0 for arguments that would be refused, and for n == 0): 4 bytes per roster key, ~4 bytes per ballot.  The roll must not be read
+ * or written by anything else while a cast that was given it is in flight.  eg_roll_cast / eg_roll_check: the same on host arrays
+ * (the roll in and out), synchronous, with their own scratch.
+ * EG_ERR_BAD_ARG before anything is launched: n >= 2^31; n_keys == 0 with n > 0; n_keys > EG_ROLL_KEYS_MAX; seq_base + n > 2^63 - 1; a
+ * policy other than the two; a NULL key_index / roll / superseded_by / found with n > 0; groups_out without roster_groups; weights_out
+ * without roster_weights; displaced without displaced_count or the reverse; a scratch that is NULL or too small; 64-bit arrays (roll,
+ * roster_weights, superseded_by, weights_out, displaced, displaced_count) that are not 8-byte aligned, 32-bit arrays (the others and the
+ * scratch) that are not 4-byte aligned.  The argument rules come before the context is looked at.  n == 0 is EG_OK: the roll is
+ * untouched, the count and the found words (where given) are zero. */
+enum { EG_ROLL_FIRST = 1, EG_ROLL_LAST = 2 };                                   /* policy */
+enum { EG_ROLL_SUPERSEDED = 1, EG_ROLL_OFF_ROLL = 2, EG_ROLL_NOT_CAST = 3 };    /* detail of EG_ST_SUPERSEDED */
+#define EG_SEQ_NONE (~(uint64_t)0)
+#define EG_ROLL_KEYS_MAX (1u << 31)
+#define EG_ROLL_SEQ_END (((uint64_t)1 << 63) - 1u)   /* seq_base + n may reach it */
+#define EG_ROLL_WORD(seq, policy) ((policy) == EG_ROLL_LAST ? (uint64_t)(seq) + 1u : EG_ROLL_SEQ_END - (uint64_t)(seq))
+#define EG_ROLL_SEQ(word, policy) ((policy) == EG_ROLL_LAST ? (uint64_t)(word) - 1u : EG_ROLL_SEQ_END - (uint64_t)(word))
+size_t eg_roll_cast_scratch_bytes(const eg_ctx*, size_t n, size_t n_keys);
+int eg_roll_cast_device(eg_ctx*, size_t n, const void* d_key_index /* uint32[n] */, const void* d_status_in /* uint32[n] or NULL */,
+                        uint64_t seq_base, int policy, void* d_roll /* uint64[n_keys], in and out */, size_t n_keys,
+                        const void* d_roster_groups /* uint32[n_keys] or NULL */, const void* d_roster_weights /* uint64[n_keys] or NULL */,
+                        void* d_superseded_by /* uint64[n] */, void* d_status_out /* uint32[n] or NULL */,
+                        void* d_groups_out /* uint32[n] or NULL */, void* d_weights_out /* uint64[n] or NULL */,
+                        void* d_displaced /* n x 2 x uint64 or NULL */, void* d_displaced_count /* uint64 or NULL */,
+                        void* d_found /* 3 x uint32 */, void* d_scratch, size_t scratch_bytes, void* stream);
+int eg_roll_cast(eg_ctx*, size_t n, const uint32_t* key_index, const uint32_t* status_in /* or NULL */, uint64_t seq_base, int policy,
+                 uint64_t* roll /* n_keys, in and out */, size_t n_keys, const uint32_t* roster_groups /* or NULL */,
+                 const uint64_t* roster_weights /* or NULL */, uint64_t* superseded_by, uint32_t* status_out /* or NULL */,
+                 uint32_t* groups_out /* or NULL */, uint64_t* weights_out /* or NULL */, uint64_t* displaced /* n x 2, or NULL */,
+                 uint64_t* displaced_count /* or NULL */, uint32_t* found /* 3 */);
+int eg_roll_check_device(eg_ctx*, size_t n, const void* d_key_index, const void* d_status_in /* or NULL */, uint64_t seq_base, int policy,
+                         const void* d_roll /* uint64[n_keys] */, size_t n_keys, const void* d_roster_groups /* or NULL */,
+                         const void* d_roster_weights /* or NULL */, void* d_superseded_by, void* d_status_out /* or NULL */,
+                         void* d_groups_out /* or NULL */, void* d_weights_out /* or NULL */, void* d_found /* 3 x uint32 */, void* stream);
+int eg_roll_check(eg_ctx*, size_t n, const uint32_t* key_index, const uint32_t* status_in /* or NULL */, uint64_t seq_base, int policy,
+                  const uint64_t* roll /* n_keys */, size_t n_keys, const uint32_t* roster_groups /* or NULL */,
+                  const uint64_t* roster_weights /* or NULL */, uint64_t* superseded_by, uint32_t* status_out /* or NULL */,
+                  uint32_t* groups_out /* or NULL */, uint64_t* weights_out /* or NULL */, uint32_t* found /* 3 */);
 
 /* ---- batch tier on several GPUs of ONE process (SURVEY.md 8b `device_mask`; the reference's host is one single-threaded process,
  * examples/voting.rs:179-213) -----------------------------------------------------------------------------------------------------

@@ -800,6 +800,83 @@ struct Ed25519 {
   }
 };
 
+// Voter roll: one counted ballot per voter, by a policy, across batches and GPUs (eg_hip.h, "voter roll" has the rule); between weeding
+// and the tally.  The roll is the caller's vector of one 64-bit word per roster key (0 = no counted ballot yet), kept between calls and
+// merged with the rolls of other slabs, ranks or GPUs by the element-wise maximum.  status_out / groups_out / weights_out are the arrays
+// ChoiceParams::tally_grouped / tally_weighted take (groups and weights only with the roster arrays).
+struct RollVerdicts {
+  std::vector<uint64_t> superseded_by;                        // EG_SEQ_NONE: kept, not participating, or without a winner
+  std::vector<uint32_t> status_out, groups_out;
+  std::vector<uint64_t> weights_out;
+  std::vector<std::pair<uint64_t, uint64_t>> displaced;       // cast only: (old sequence number, new sequence number)
+  uint32_t found[3] = {0, 0, 0};                              // superseded, displaced (check: not cast), off the roll
+};
+struct VoterRoll {
+  const Context& ctx;
+  int policy = EG_ROLL_LAST;
+  uint64_t word(uint64_t seq) const { return EG_ROLL_WORD(seq, policy); }
+  uint64_t seq(uint64_t word) const { return EG_ROLL_SEQ(word, policy); }
+  // ballot b has the sequence number seq_base + b and participates iff status_in[b] == 0 (empty: every ballot); `roll` is updated
+  RollVerdicts cast(const std::vector<uint32_t>& key_index, std::vector<uint64_t>& roll, uint64_t seq_base = 0, const std::vector<uint32_t>& status_in = {},
+                    const std::vector<uint32_t>& roster_groups = {}, const std::vector<uint64_t>& roster_weights = {}) const {
+    RollVerdicts v = room(key_index, roll, status_in, roster_groups, roster_weights);
+    const size_t n = key_index.size();
+    std::vector<uint64_t> pairs(2 * n);
+    uint64_t count = 0;
+    ok(eg_roll_cast(ctx.raw(), n, key_index.data(), status_in.empty() ? nullptr : status_in.data(), seq_base, policy, roll.data(), roll.size(),
+                       roster_groups.empty() ? nullptr : roster_groups.data(), roster_weights.empty() ? nullptr : roster_weights.data(),
+                       v.superseded_by.data(), v.status_out.data(), roster_groups.empty() ? nullptr : v.groups_out.data(),
+                       roster_weights.empty() ? nullptr : v.weights_out.data(), pairs.data(), &count, v.found));
+    for (uint64_t k = 0; k < count; ++k) v.displaced.emplace_back(pairs[2 * k], pairs[2 * k + 1]);
+    return v;
+  }
+  // the same verdicts against a read-only roll: the final one at the close of the election, or a merged one
+  RollVerdicts check(const std::vector<uint32_t>& key_index, const std::vector<uint64_t>& roll, uint64_t seq_base = 0,
+                     const std::vector<uint32_t>& status_in = {}, const std::vector<uint32_t>& roster_groups = {},
+                     const std::vector<uint64_t>& roster_weights = {}) const {
+    RollVerdicts v = room(key_index, roll, status_in, roster_groups, roster_weights);
+    ok(eg_roll_check(ctx.raw(), key_index.size(), key_index.data(), status_in.empty() ? nullptr : status_in.data(), seq_base, policy,
+                                            roll.data(), roll.size(), roster_groups.empty() ? nullptr : roster_groups.data(),
+                                            roster_weights.empty() ? nullptr : roster_weights.data(), v.superseded_by.data(), v.status_out.data(),
+                                            roster_groups.empty() ? nullptr : v.groups_out.data(), roster_weights.empty() ? nullptr : v.weights_out.data(),
+                                            v.found));
+    return v;
+  }
+  // asynchronous device-pointer forms: no allocation, no synchronisation, no lock; d_scratch of cast_scratch_bytes(n, n_keys) bytes;
+  // d_status_out may be d_status_in; d_displaced (n x 2 x uint64) comes with d_displaced_count (uint64), or both are null
+  size_t cast_scratch_bytes(size_t n, size_t n_keys) const { return eg_roll_cast_scratch_bytes(ctx.raw(), n, n_keys); }
+  void cast_device(size_t n, const void* d_key_index, const void* d_status_in, uint64_t seq_base, void* d_roll, size_t n_keys,
+                   const void* d_roster_groups, const void* d_roster_weights, void* d_superseded_by, void* d_status_out, void* d_groups_out,
+                   void* d_weights_out, void* d_displaced, void* d_displaced_count, void* d_found, void* d_scratch, size_t scratch_bytes,
+                   void* stream = nullptr) const {
+    ok(eg_roll_cast_device(ctx.raw(), n, d_key_index, d_status_in, seq_base, policy, d_roll, n_keys, d_roster_groups,
+                                                  d_roster_weights, d_superseded_by, d_status_out, d_groups_out, d_weights_out, d_displaced,
+                                                  d_displaced_count, d_found, d_scratch, scratch_bytes, stream));
+  }
+  void check_device(size_t n, const void* d_key_index, const void* d_status_in, uint64_t seq_base, const void* d_roll, size_t n_keys,
+                    const void* d_roster_groups, const void* d_roster_weights, void* d_superseded_by, void* d_status_out, void* d_groups_out,
+                    void* d_weights_out, void* d_found, void* stream = nullptr) const {
+    ok(eg_roll_check_device(ctx.raw(), n, d_key_index, d_status_in, seq_base, policy, d_roll, n_keys, d_roster_groups,
+                                                   d_roster_weights, d_superseded_by, d_status_out, d_groups_out, d_weights_out, d_found, stream));
+  }
+
+ private:
+  // the member `check` hides the free function of the namespace
+  static void ok(int rc) { if (rc != EG_OK) throw Error(rc, eg_last_error()); }
+  static RollVerdicts room(const std::vector<uint32_t>& key_index, const std::vector<uint64_t>& roll, const std::vector<uint32_t>& status_in,
+                           const std::vector<uint32_t>& roster_groups, const std::vector<uint64_t>& roster_weights) {
+    const size_t n = key_index.size();
+    if ((!status_in.empty() && status_in.size() != n) || (!roster_groups.empty() && roster_groups.size() != roll.size()) ||
+        (!roster_weights.empty() && roster_weights.size() != roll.size()))
+      throw Error(EG_ERR_BAD_ARG, "one status word per ballot, one group and one weight per roster key");
+    RollVerdicts v;
+    v.superseded_by.resize(n); v.status_out.resize(n);
+    if (!roster_groups.empty()) v.groups_out.resize(n);
+    if (!roster_weights.empty()) v.weights_out.resize(n);
+    return v;
+  }
+};
+
 // ---- tally stage (examples/voting.rs:122-177) ------------------------------------------------------------------------------------
 // Params::combine_shares (sharing/mod.rs:302-325): the first `threshold` of the given (participant index, dh element) pairs ->
 // the combined decryption [x]R, or nullopt when there are too few shares.  Verify the shares first (eg_share_params_create).
