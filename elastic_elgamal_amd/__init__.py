@@ -20,7 +20,7 @@ import os
 from pathlib import Path
 
 __all__ = [
-    "Context", "Ristretto", "Ed25519", "VoterRoll", "ChoiceParams", "QuadraticVotingParams", "PublicKeyVerifier", "DecryptionShareVerifier", "SumOfSquaresVerifier", "EgError", "library_path", "build",
+    "Context", "Ristretto", "Ed25519", "VoterRoll", "ReceiptLog", "ChoiceParams", "QuadraticVotingParams", "PublicKeyVerifier", "DecryptionShareVerifier", "SumOfSquaresVerifier", "EgError", "library_path", "build",
     "STATUS_NAMES", "status_kind", "status_detail", "pack_json", "JsonPacker", "PACK_RESHAPE", "verify_json_multi", "json_stream_multi",
 ]
 
@@ -217,6 +217,19 @@ def _load() -> C.CDLL:
         "eg_roll_cast": (C.c_int, [vp, sz, vp, vp, C.c_uint64, C.c_int, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "eg_roll_check_device": (C.c_int, [vp, sz, vp, vp, C.c_uint64, C.c_int, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp]),
         "eg_roll_check": (C.c_int, [vp, sz, vp, vp, C.c_uint64, C.c_int, vp, sz, vp, vp, vp, vp, vp, vp, vp]),
+        "eg_merkle_depth": (C.c_int, [C.c_uint64]),
+        "eg_merkle_nodes_bytes": (sz, [C.c_uint64]),
+        "eg_merkle_level": (C.c_int, [C.c_uint64, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+        "eg_merkle_leaves_scratch_bytes": (sz, [sz]),
+        "eg_merkle_tree_scratch_bytes": (sz, [C.c_uint64]),
+        "eg_merkle_leaves_device": (C.c_int, [vp, sz, vp, sz, sz, cp, sz, vp, sz, sz, vp, C.c_uint64, vp, vp, vp, C.c_uint64, vp, vp, vp, sz, vp]),
+        "eg_merkle_leaves": (C.c_int, [vp, sz, cp, sz, sz, cp, sz, cp, sz, sz, vp, C.c_uint64, vp, vp, vp, C.c_uint64, vp, vp]),
+        "eg_merkle_tree_device": (C.c_int, [vp, C.c_uint64, vp, vp, vp, vp, sz, vp]),
+        "eg_merkle_tree": (C.c_int, [vp, C.c_uint64, cp, vp, vp]),
+        "eg_merkle_paths_device": (C.c_int, [vp, sz, vp, C.c_uint64, vp, vp, vp, vp, vp]),
+        "eg_merkle_paths": (C.c_int, [vp, sz, vp, C.c_uint64, cp, cp, vp, vp]),
+        "eg_merkle_check_device": (C.c_int, [vp, sz, vp, vp, vp, sz, vp, C.c_uint64, vp, vp, vp, vp]),
+        "eg_merkle_check": (C.c_int, [vp, sz, vp, cp, cp, sz, vp, C.c_uint64, cp, vp, vp]),
         "eg_proof_params_create": (C.c_int, [vp, cp, C.c_int, C.c_uint64, C.POINTER(vp)]),
         "eg_share_params_create": (C.c_int, [vp, cp, C.c_uint64, C.c_uint64, C.c_uint64, cp, C.POINTER(vp)]),
         "eg_proof_params_destroy": (None, [vp]),
@@ -293,6 +306,11 @@ ROLL_FIRST, ROLL_LAST = 1, 2     # include/eg_hip.h: EG_ROLL_FIRST / EG_ROLL_LAS
 ROLL_SUPERSEDED, ROLL_OFF_ROLL, ROLL_NOT_CAST = 1, 2, 3
 SEQ_NONE = (1 << 64) - 1         # include/eg_hip.h: EG_SEQ_NONE
 ROLL_KEYS_MAX = 1 << 31          # include/eg_hip.h: EG_ROLL_KEYS_MAX
+MERKLE_BAD_INDEX, MERKLE_BAD_LENGTH, MERKLE_MISMATCH = 1, 2, 3    # include/eg_hip.h: EG_MERKLE_*, the verdict of a receipt
+MERKLE_HASH_BYTES = 32           # include/eg_hip.h: EG_MERKLE_HASH_BYTES
+MERKLE_LEAVES_MAX = 1 << 31      # include/eg_hip.h: EG_MERKLE_LEAVES_MAX
+LEAF_NONE = (1 << 64) - 1        # include/eg_hip.h: EG_LEAF_NONE, the leaf_index of a ballot that does not participate
+MERKLE_NO_PATH = 0xFFFFFFFF      # include/eg_hip.h: EG_MERKLE_NO_PATH, the path_len of an index that is not in the log
 
 
 def pack_json(text, n_options: int, single: bool | None = None, credits: int | None = None, threads: int = 0, max_objects: int = 0):
@@ -741,6 +759,135 @@ class VoterRoll:
         _check(_load().eg_roll_check_device(self.ctx._h, n, d_key_index or None, d_status_in or None, seq_base, self.policy, d_roll or None, n_keys,
                                             d_roster_groups or None, d_roster_weights or None, d_superseded_by or None, d_status_out or None,
                                             d_groups_out or None, d_weights_out or None, d_found or None, stream or None))
+
+
+class LeafResult:
+    """What ReceiptLog.leaves says about a batch: leaf_index per ballot (LEAF_NONE: it does not participate), leaves = the n x 32 bytes of
+    leaves_out (zeroed rows for ballots that do not participate), log = the caller's log with the participating leaves appended (None
+    without an append), found = (number of leaves, non-zero: the append did not fit)."""
+
+    def __init__(self, leaf_index, leaves, log, found):
+        self.leaf_index, self.leaves, self.log, self.found = leaf_index, leaves, log, found
+
+
+class ReceiptLog:
+    """Ballot receipts (include/eg_hip.h, "receipt log" has the rule): a Merkle tree (RFC 6962, H = the first 32 bytes of SHA-512) over
+    the posted ballots.  The log is the caller's bytes of 32-byte leaves, normally fed weeding's status_out; `prefix` is the election id.
+    Every tree() is a full rebuild; there is no incremental frontier state."""
+
+    BAD_INDEX, BAD_LENGTH, MISMATCH = MERKLE_BAD_INDEX, MERKLE_BAD_LENGTH, MERKLE_MISMATCH
+    HASH_BYTES, LEAVES_MAX, LEAF_NONE, NO_PATH = MERKLE_HASH_BYTES, MERKLE_LEAVES_MAX, LEAF_NONE, MERKLE_NO_PATH
+
+    def __init__(self, ctx: Context, prefix: bytes = b""):
+        self.ctx, self.prefix = ctx, bytes(prefix)
+
+    @staticmethod
+    def depth(n_leaves: int) -> int:
+        """eg_merkle_depth: ceil(log2 N), 0 for N <= 1 (pure host arithmetic)."""
+        return int(_load().eg_merkle_depth(n_leaves))
+
+    @staticmethod
+    def nodes_bytes(n_leaves: int) -> int:
+        """eg_merkle_nodes_bytes: the size of the node store (levels 1 .. depth back to back)."""
+        return int(_load().eg_merkle_nodes_bytes(n_leaves))
+
+    @staticmethod
+    def level(n_leaves: int, level: int):
+        """eg_merkle_level: (byte offset into the node store, node count) of a level; level 0 is the log itself."""
+        off, count = C.c_uint64(0), C.c_uint64(0)
+        _check(_load().eg_merkle_level(n_leaves, level, C.byref(off), C.byref(count)))
+        return int(off.value), int(count.value)
+
+    def leaves(self, msgs: bytes, msg_len: int, extra: bytes = None, extra_len: int = 0, status_in=None, log: bytes = None, log_cap: int = None,
+               n_prior: int = None, stride=None, extra_stride=None, n=None) -> LeafResult:
+        """eg_merkle_leaves: the leaf of every participating ballot (status_in None: all).  With `log` (bytes of earlier leaves) the
+        participating leaves are appended behind it, at most log_cap entries in all (None: whatever is needed); without one n_prior
+        (default 0) still counts into leaf_index.  Raises EgError after the outputs are lost if the append does not fit."""
+        n, stride = Ed25519._n(msgs, msg_len, stride, n)
+        extra_stride = extra_len if extra_stride is None else extra_stride
+        append = log is not None
+        if append:
+            n_prior = len(log) // MERKLE_HASH_BYTES
+            log_cap = n_prior + n if log_cap is None else log_cap
+        n_prior = n_prior or 0
+        sin = (C.c_uint32 * max(n, 1))(*status_in) if status_in is not None else None
+        idx = (C.c_uint64 * max(n, 1))()
+        out = C.create_string_buffer(MERKLE_HASH_BYTES * max(n, 1))
+        room = None
+        if append:
+            room = C.create_string_buffer(MERKLE_HASH_BYTES * max(log_cap, n_prior, 1))
+            C.memmove(room, bytes(log), MERKLE_HASH_BYTES * n_prior)
+        count, found = C.c_uint64(0), (C.c_uint32 * 2)()
+        _check(_load().eg_merkle_leaves(self.ctx._h, n, msgs, stride, msg_len, self.prefix or None, len(self.prefix), extra if extra_len else None,
+                                        extra_stride, extra_len, sin, n_prior, idx, out, room, log_cap or 0, C.byref(count) if append else None, found))
+        return LeafResult(list(idx[:n]), out.raw[: MERKLE_HASH_BYTES * n], room.raw[: MERKLE_HASH_BYTES * count.value] if append else None, list(found))
+
+    def tree(self, log: bytes, with_nodes: bool = True):
+        """eg_merkle_tree: (root, node store or None) over the len(log) / 32 leaves of the log; a full rebuild."""
+        n = len(log) // MERKLE_HASH_BYTES
+        root = C.create_string_buffer(MERKLE_HASH_BYTES)
+        size = self.nodes_bytes(n)
+        nodes = C.create_string_buffer(max(size, 1)) if with_nodes else None
+        _check(_load().eg_merkle_tree(self.ctx._h, n, log or None, root, nodes))
+        return root.raw, (nodes.raw[:size] if with_nodes else None)
+
+    def paths(self, index, log: bytes, nodes: bytes):
+        """eg_merkle_paths: ([path bytes per requested leaf, or None for an index that is not in the log], the raw rows, path_len)."""
+        n, m = len(log) // MERKLE_HASH_BYTES, len(index)
+        row = MERKLE_HASH_BYTES * self.depth(n)
+        idx = (C.c_uint64 * max(m, 1))(*index)
+        out = C.create_string_buffer(max(m * row, 1))
+        lens = (C.c_uint32 * max(m, 1))()
+        _check(_load().eg_merkle_paths(self.ctx._h, m, idx, n, log or None, nodes or None, out if row else None, lens))
+        rows = out.raw[: m * row]
+        paths = [None if lens[j] == MERKLE_NO_PATH else rows[j * row: j * row + MERKLE_HASH_BYTES * lens[j]] for j in range(m)]
+        return paths, rows, list(lens[:m])
+
+    def check(self, index, leaves: bytes, paths, n_leaves: int, root: bytes, path_len=None, path_stride=None):
+        """eg_merkle_check: (verdicts, found).  `paths` is a list of path bytes (their lengths are the path_len), or raw rows with path_len
+        and path_stride given."""
+        m = len(index)
+        if path_len is None:
+            path_len = [len(p) // MERKLE_HASH_BYTES for p in paths]
+            path_stride = max([MERKLE_HASH_BYTES * self.depth(n_leaves)] + [len(p) for p in paths])
+            paths = b"".join(p + bytes(path_stride - len(p)) for p in paths)
+        idx = (C.c_uint64 * max(m, 1))(*index)
+        lens = (C.c_uint32 * max(m, 1))(*path_len)
+        verdict, found = (C.c_uint32 * max(m, 1))(), (C.c_uint32 * 3)()
+        _check(_load().eg_merkle_check(self.ctx._h, m, idx, leaves, paths or None, path_stride, lens, n_leaves, root, verdict, found))
+        return list(verdict[:m]), list(found)
+
+    @staticmethod
+    def leaves_scratch_bytes(n: int) -> int:
+        return int(_load().eg_merkle_leaves_scratch_bytes(n))
+
+    @staticmethod
+    def tree_scratch_bytes(n_leaves: int) -> int:
+        """Scratch of tree_device WITHOUT a node store (0 up to 1024 leaves)."""
+        return int(_load().eg_merkle_tree_scratch_bytes(n_leaves))
+
+    def leaves_device(self, n: int, d_msgs: int, msg_stride: int, msg_len: int, d_leaf_index: int, d_found: int, d_scratch: int, scratch_bytes: int,
+                      d_extra: int = 0, extra_stride: int = 0, extra_len: int = 0, d_status_in: int = 0, n_prior: int = 0, d_leaves_out: int = 0,
+                      d_log: int = 0, log_cap: int = 0, d_log_count: int = 0, stream: int = 0):
+        """Asynchronous device-pointer variant (eg_merkle_leaves_device): no allocation, no host synchronisation, no lock.  d_leaf_index: n
+        uint64; d_found: 2 uint32; d_log (log_cap x 32) with d_log_count (uint64) requests the append."""
+        _check(_load().eg_merkle_leaves_device(self.ctx._h, n, d_msgs or None, msg_stride, msg_len, self.prefix or None, len(self.prefix),
+                                               d_extra or None, extra_stride, extra_len, d_status_in or None, n_prior, d_leaf_index or None,
+                                               d_leaves_out or None, d_log or None, log_cap, d_log_count or None, d_found or None,
+                                               d_scratch or None, scratch_bytes, stream or None))
+
+    def tree_device(self, n_leaves: int, d_log: int, d_root: int, d_nodes: int = 0, d_scratch: int = 0, scratch_bytes: int = 0, stream: int = 0):
+        _check(_load().eg_merkle_tree_device(self.ctx._h, n_leaves, d_log or None, d_root or None, d_nodes or None, d_scratch or None, scratch_bytes,
+                                             stream or None))
+
+    def paths_device(self, m: int, d_index: int, n_leaves: int, d_log: int, d_nodes: int, d_paths: int, d_path_len: int, stream: int = 0):
+        _check(_load().eg_merkle_paths_device(self.ctx._h, m, d_index or None, n_leaves, d_log or None, d_nodes or None, d_paths or None,
+                                              d_path_len or None, stream or None))
+
+    def check_device(self, m: int, d_index: int, d_leaves: int, d_paths: int, path_stride: int, d_path_len: int, n_leaves: int, d_root: int,
+                     d_verdict: int, d_found: int, stream: int = 0):
+        _check(_load().eg_merkle_check_device(self.ctx._h, m, d_index or None, d_leaves or None, d_paths or None, path_stride, d_path_len or None,
+                                              n_leaves, d_root or None, d_verdict or None, d_found or None, stream or None))
 
 
 def prepared_point_size() -> int:

@@ -36,6 +36,7 @@
 #include "weed_kernels.cuh"
 #include "ed25519_kernels.cuh"
 #include "roll_kernels.cuh"
+#include "merkle_kernels.cuh"
 
 using namespace eg;
 
@@ -4360,6 +4361,258 @@ int eg_roll_check(eg_ctx* c, size_t n, const uint32_t* key_index, const uint32_t
                   uint32_t* groups_out, uint64_t* weights_out, uint32_t* found) {
   return roll_host(c, false, n, key_index, status_in, seq_base, policy, roll, nullptr, n_keys, roster_groups, roster_weights, superseded_by,
                    status_out, groups_out, weights_out, nullptr, nullptr, found);
+}
+
+// ---- receipt log: leaf hashes, the Merkle tree above them, audit paths and their check (merkle_kernels.cuh; the rule: include/eg_hip.h) ----
+// Stateless like weeding and the roll: everything is the caller's - no lock, no workspace of the context, no allocation, no synchronisation
+// in the _device forms.  The argument rules come first and need no context (so they can be tested without a GPU); what passes them fails on
+// a null context.
+static int merkle_refuse(const char* why) { return why ? fail(EG_ERR_BAD_ARG, std::string("merkle: ") + why) : EG_OK; }
+static int merkle_check_ctx(const eg_ctx* c) { return c ? EG_OK : fail(EG_ERR_BAD_ARG, "merkle: null ctx"); }
+static int merkle_check_aligned(uintptr_t words64, uintptr_t words32) {
+  if (words64 & 7u) return fail(EG_ERR_BAD_ARG, "merkle: leaf_index, log_count and index must be 8-byte aligned");
+  if (words32 & 3u) return fail(EG_ERR_BAD_ARG, "merkle: leaves, log, nodes, paths, root, path_len, verdict, the status words, found and scratch must be 4-byte aligned");
+  return EG_OK;
+}
+int eg_merkle_depth(uint64_t n_leaves) { return egm::depth(n_leaves); }
+size_t eg_merkle_nodes_bytes(uint64_t n_leaves) { return n_leaves < egm::LEAVES_MAX ? (size_t)egm::nodes_total(n_leaves) * egm::HASH_BYTES : 0; }
+int eg_merkle_level(uint64_t n_leaves, int level, uint64_t* offset, uint64_t* count) {
+  if (n_leaves >= egm::LEAVES_MAX) return merkle_refuse("N is 2^31 or more");
+  if (level < 0 || level > egm::depth(n_leaves)) return merkle_refuse("level is not in 0 .. depth(N)");
+  if (!offset || !count) return merkle_refuse("null offset or count");
+  *offset = level ? egm::level_offset(n_leaves, level) * egm::HASH_BYTES : 0u;
+  *count = egm::level_count(n_leaves, level);
+  return EG_OK;
+}
+size_t eg_merkle_leaves_scratch_bytes(size_t n) { return n < egm::LEAVES_MAX ? egm::leaf_layout(n).total : 0; }
+size_t eg_merkle_tree_scratch_bytes(uint64_t n_leaves) { return n_leaves < egm::LEAVES_MAX ? egm::tree_layout(n_leaves).total : 0; }
+
+// the launches of the leaf pass; `tail` = entry n_prior of the log with room for `room` entries, or null: no append
+static int merkle_leaves_run(eg_ctx* c, size_t n, MerkleItems it, const uint8_t* prefix, size_t prefix_len, const u32* status, uint64_t n_prior,
+                             void* d_leaf_index, void* d_leaves_out, u32* tail, uint64_t room, void* d_log_count, void* d_found, void* d_scratch,
+                             hipStream_t s) {
+  HIPCHK(hipSetDevice(c->device));
+  u32* found = static_cast<u32*>(d_found);
+  unsigned long long* count = static_cast<unsigned long long*>(d_log_count);
+  if (n == 0) {                                                         // no leaves: the count is n_prior, the found words are zero
+    if (found || count) hipLaunchKernelGGL(k_merkle_scan_tops, dim3(1), dim3(64), 0, s, 0u, (u32*)nullptr, n_prior, room, (u32*)nullptr, count, found);
+    HIPCHK(hipGetLastError());
+    return EG_OK;
+  }
+  const egm::LeafLayout L = egm::leaf_layout(n);
+  char* base = static_cast<char*>(d_scratch);
+  unsigned char* head = reinterpret_cast<unsigned char*>(base + L.head);
+  u32* pos = reinterpret_cast<u32*>(base + L.pos);
+  u32* tiles = reinterpret_cast<u32*>(base + L.tiles);
+  u32* total_word = reinterpret_cast<u32*>(base + L.total_word);
+  u32* rows = d_leaves_out ? static_cast<u32*>(d_leaves_out) : reinterpret_cast<u32*>(base + L.leaves);
+  HIPCHK(hipMemsetAsync(head, 0, 1, s));                                // the domain byte of a leaf
+  if (prefix_len) HIPCHK(hipMemcpyAsync(head + 1, prefix, prefix_len, hipMemcpyHostToDevice, s));
+  it.head = head;
+  it.head_len = 1 + prefix_len;
+  const MerkleLeafDev leaf{it, rows, d_leaves_out != nullptr, pos};
+  const MerklePlaceDev place{pos, rows, static_cast<unsigned long long*>(d_leaf_index), tail};
+  hipLaunchKernelGGL(k_merkle_leaf, dim3((unsigned)((n + MERKLE_NT - 1) / MERKLE_NT)), dim3(MERKLE_NT), 0, s, leaf, status, (uint64_t)n);
+  hipLaunchKernelGGL(k_merkle_scan_tiles, dim3(L.n_tiles), dim3(MERKLE_NT), 0, s, (const u32*)pos, (u32)n, tiles);
+  hipLaunchKernelGGL(k_merkle_scan_tops, dim3(1), dim3(64), 0, s, L.n_tiles, tiles, n_prior, room, total_word, count, found);
+  hipLaunchKernelGGL(k_merkle_scan_apply, dim3(L.n_tiles), dim3(MERKLE_NT), 0, s, pos, (u32)n, (const u32*)tiles);
+  hipLaunchKernelGGL(k_merkle_place, dim3((unsigned)((n * 8 + MERKLE_NT - 1) / MERKLE_NT)), dim3(MERKLE_NT), 0, s, place, (uint64_t)n, n_prior, room,
+                     (const u32*)total_word);
+  HIPCHK(hipGetLastError());
+  return EG_OK;
+}
+int eg_merkle_leaves_device(eg_ctx* c, size_t n, const void* d_msgs, size_t msg_stride, size_t msg_len, const uint8_t* prefix, size_t prefix_len,
+                            const void* d_extra, size_t extra_stride, size_t extra_len, const void* d_status_in, uint64_t n_prior,
+                            void* d_leaf_index, void* d_leaves_out, void* d_log, uint64_t log_cap, void* d_log_count, void* d_found,
+                            void* d_scratch, size_t scratch_bytes, void* stream) {
+  TRY_(merkle_refuse(egm::refuse_messages(n, d_msgs != nullptr, msg_stride, msg_len, prefix != nullptr, prefix_len, d_extra != nullptr, extra_stride,
+                                          extra_len)));
+  TRY_(merkle_refuse(egm::refuse_leaves(n, n_prior, d_leaf_index != nullptr, d_found != nullptr, d_log != nullptr, d_log_count != nullptr, log_cap)));
+  TRY_(merkle_check_aligned((uintptr_t)d_leaf_index | (uintptr_t)d_log_count,
+                            (uintptr_t)d_leaves_out | (uintptr_t)d_log | (uintptr_t)d_status_in | (uintptr_t)d_found | (uintptr_t)d_scratch));
+  const size_t need = egm::leaf_layout(n).total;
+  if (need && (!d_scratch || scratch_bytes < need)) return merkle_refuse("scratch is null or too small (eg_merkle_leaves_scratch_bytes says how much)");
+  TRY_(merkle_check_ctx(c));
+  const MerkleItems it{static_cast<const unsigned char*>(d_msgs), msg_stride, msg_len, extra_len ? static_cast<const unsigned char*>(d_extra) : nullptr,
+                       extra_stride, extra_len, nullptr, 0};
+  u32* tail = d_log_count ? static_cast<u32*>(d_log) + n_prior * egm::HASH_WORDS : nullptr;
+  return merkle_leaves_run(c, n, it, prefix, prefix_len, static_cast<const u32*>(d_status_in), n_prior, d_leaf_index, d_leaves_out, tail,
+                           d_log_count ? log_cap - n_prior : 0u, d_log_count, d_found, d_scratch, (hipStream_t)stream);
+}
+int eg_merkle_leaves(eg_ctx* c, size_t n, const uint8_t* msgs, size_t msg_stride, size_t msg_len, const uint8_t* prefix, size_t prefix_len,
+                     const uint8_t* extra, size_t extra_stride, size_t extra_len, const uint32_t* status_in, uint64_t n_prior, uint64_t* leaf_index,
+                     uint8_t* leaves_out, uint8_t* log, uint64_t log_cap, uint64_t* log_count, uint32_t* found) {
+  TRY_(merkle_refuse(egm::refuse_messages(n, msgs != nullptr, msg_stride, msg_len, prefix != nullptr, prefix_len, extra != nullptr, extra_stride, extra_len)));
+  TRY_(merkle_refuse(egm::refuse_leaves(n, n_prior, leaf_index != nullptr, found != nullptr, log != nullptr, log_count != nullptr, log_cap)));
+  TRY_(merkle_check_ctx(c));
+  if (found) found[0] = found[1] = 0;
+  if (log_count) *log_count = n_prior;
+  if (n == 0) return EG_OK;
+  HIPCHK(hipSetDevice(c->device));
+  EdStage st; st.who = "merkle"; TRY_(st.open());
+  const size_t need = eg_merkle_leaves_scratch_bytes(n);
+  const uint64_t room = log_count ? log_cap - n_prior : 0u;
+  const size_t tail_rows = (size_t)std::min<uint64_t>(room, n);       // at most n leaves are appended, and never more than fit
+  void *dm = nullptr, *de = nullptr, *dsi = nullptr, *di, *dl = nullptr, *dt = nullptr, *dtail, *scratch;
+  if (msg_len) TRY_(st.put(&dm, msgs, ed_msgs_bytes(n, msg_stride, msg_len)));
+  if (extra_len) TRY_(st.put(&de, extra, ed_msgs_bytes(n, extra_stride, extra_len)));
+  if (status_in) TRY_(st.put(&dsi, status_in, n * 4));
+  TRY_(st.put(&di, nullptr, n * 8));
+  if (leaves_out) TRY_(st.put(&dl, nullptr, n * egm::HASH_BYTES));
+  if (log_count) TRY_(st.put(&dt, nullptr, tail_rows * egm::HASH_BYTES));
+  TRY_(st.put(&dtail, nullptr, 32));                                    // the count (uint64), then the two found words
+  TRY_(st.put(&scratch, nullptr, need));
+  void* d_count = log_count ? dtail : nullptr;
+  void* d_found = static_cast<char*>(dtail) + 8;
+  const MerkleItems it{static_cast<const unsigned char*>(dm), msg_stride, msg_len, static_cast<const unsigned char*>(de), extra_stride, extra_len, nullptr, 0};
+  TRY_(merkle_leaves_run(c, n, it, prefix, prefix_len, static_cast<const u32*>(dsi), n_prior, di, dl, static_cast<u32*>(dt), room, d_count, d_found,
+                         scratch, st.s));
+  unsigned long long count = n_prior;
+  HIPCHK(hipMemcpyAsync(leaf_index, di, n * 8, hipMemcpyDeviceToHost, st.s));
+  if (leaves_out) HIPCHK(hipMemcpyAsync(leaves_out, dl, n * egm::HASH_BYTES, hipMemcpyDeviceToHost, st.s));
+  HIPCHK(hipMemcpyAsync(found, d_found, 2 * sizeof(u32), hipMemcpyDeviceToHost, st.s));
+  if (log_count) HIPCHK(hipMemcpyAsync(&count, d_count, sizeof count, hipMemcpyDeviceToHost, st.s));
+  HIPCHK(hipStreamSynchronize(st.s));
+  if (log_count && count > n_prior && count - n_prior <= tail_rows) {
+    HIPCHK(hipMemcpyAsync(log + n_prior * egm::HASH_BYTES, dt, (size_t)(count - n_prior) * egm::HASH_BYTES, hipMemcpyDeviceToHost, st.s));
+    HIPCHK(hipStreamSynchronize(st.s));
+  }
+  if (log_count) *log_count = count;
+  if (found[1]) return fail(EG_ERR_BAD_ARG, "merkle: the leaves do not fit the log (log_cap); nothing was appended");
+  return EG_OK;
+}
+
+int eg_merkle_tree_device(eg_ctx* c, uint64_t n_leaves, const void* d_log, void* d_root, void* d_nodes, void* d_scratch, size_t scratch_bytes,
+                          void* stream) {
+  TRY_(merkle_refuse(egm::refuse_tree(n_leaves, d_log != nullptr, d_root != nullptr)));
+  TRY_(merkle_check_aligned(0, (uintptr_t)d_log | (uintptr_t)d_root | (uintptr_t)d_nodes | (uintptr_t)d_scratch));
+  const egm::TreeLayout L = egm::tree_layout(n_leaves);
+  if (!d_nodes && L.total && (!d_scratch || scratch_bytes < L.total))
+    return merkle_refuse("scratch is null or too small (eg_merkle_tree_scratch_bytes says how much a tree without a node store needs)");
+  TRY_(merkle_check_ctx(c));
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)stream;
+  const u32* cur = static_cast<const u32*>(d_log);
+  if (n_leaves == 0) cur = nullptr;
+  char* base = static_cast<char*>(d_scratch);
+  u32* store = static_cast<u32*>(d_nodes);
+  const int depth = egm::depth(n_leaves);
+  uint64_t n_in = n_leaves;
+  bool pong = false;
+  for (int level = 0; level < depth; pong = !pong) {
+    MerkleTileArgs a;
+    a.in = cur; a.n_in = n_in; a.store = store; a.steps = std::min(egm::T_LOG, depth - level);
+    for (int k = 0; k < egm::T_LOG; ++k) a.off[k] = k < a.steps ? egm::level_offset(n_leaves, level + k + 1) : 0u;
+    // without a store: the top level of the launch goes to the scratch, that of the last launch - one node - straight to the root
+    const bool last = level + a.steps == depth;
+    a.top = store ? nullptr : last ? static_cast<u32*>(d_root) : reinterpret_cast<u32*>(base + (pong ? L.pong : L.ping));
+    const unsigned tiles = (unsigned)((n_in + (1u << egm::T_LOG) - 1) >> egm::T_LOG);
+    hipLaunchKernelGGL(k_merkle_tile<egm::T_LOG>, dim3(tiles), dim3(1 << (egm::T_LOG - 2)), 0, s, a);
+    cur = store ? store + a.off[a.steps - 1] * egm::HASH_WORDS : a.top;
+    n_in = egm::level_count(n_in, a.steps);
+    level += a.steps;
+  }
+  if (cur != static_cast<const u32*>(d_root)) hipLaunchKernelGGL(k_merkle_root, dim3(1), dim3(64), 0, s, cur, static_cast<u32*>(d_root));
+  HIPCHK(hipGetLastError());
+  return EG_OK;
+}
+int eg_merkle_tree(eg_ctx* c, uint64_t n_leaves, const uint8_t* log, uint8_t* root, uint8_t* nodes) {
+  TRY_(merkle_refuse(egm::refuse_tree(n_leaves, log != nullptr, root != nullptr)));
+  TRY_(merkle_check_ctx(c));
+  HIPCHK(hipSetDevice(c->device));
+  EdStage st; st.who = "merkle"; TRY_(st.open());
+  const size_t store_bytes = eg_merkle_nodes_bytes(n_leaves), need = nodes ? 0 : eg_merkle_tree_scratch_bytes(n_leaves);
+  void *dl = nullptr, *dr, *dn = nullptr, *scratch = nullptr;
+  if (n_leaves) TRY_(st.put(&dl, log, (size_t)n_leaves * egm::HASH_BYTES));
+  TRY_(st.put(&dr, nullptr, egm::HASH_BYTES));
+  if (nodes) TRY_(st.put(&dn, nullptr, store_bytes));
+  if (need) TRY_(st.put(&scratch, nullptr, need));
+  TRY_(eg_merkle_tree_device(c, n_leaves, dl, dr, dn, scratch, need, st.s));
+  HIPCHK(hipMemcpyAsync(root, dr, egm::HASH_BYTES, hipMemcpyDeviceToHost, st.s));
+  if (nodes && store_bytes) HIPCHK(hipMemcpyAsync(nodes, dn, store_bytes, hipMemcpyDeviceToHost, st.s));
+  HIPCHK(hipStreamSynchronize(st.s));
+  return EG_OK;
+}
+
+int eg_merkle_paths_device(eg_ctx* c, size_t m, const void* d_index, uint64_t n_leaves, const void* d_log, const void* d_nodes, void* d_paths,
+                           void* d_path_len, void* stream) {
+  TRY_(merkle_refuse(egm::refuse_paths(m, n_leaves, d_index != nullptr, d_log != nullptr, d_nodes != nullptr, d_paths != nullptr, d_path_len != nullptr)));
+  TRY_(merkle_check_aligned((uintptr_t)d_index, (uintptr_t)d_log | (uintptr_t)d_nodes | (uintptr_t)d_paths | (uintptr_t)d_path_len));
+  TRY_(merkle_check_ctx(c));
+  if (m == 0) return EG_OK;
+  HIPCHK(hipSetDevice(c->device));
+  const int depth = egm::depth(n_leaves);
+  const MerklePathDev mem{static_cast<const u32*>(d_log), static_cast<const u32*>(d_nodes), static_cast<u32*>(d_paths), egm::HASH_WORDS * (size_t)depth};
+  hipLaunchKernelGGL(k_merkle_paths, dim3((unsigned)((m + MERKLE_NT - 1) / MERKLE_NT)), dim3(MERKLE_NT), 0, (hipStream_t)stream, mem,
+                     static_cast<const unsigned long long*>(d_index), (uint64_t)m, n_leaves, depth, static_cast<u32*>(d_path_len));
+  HIPCHK(hipGetLastError());
+  return EG_OK;
+}
+int eg_merkle_paths(eg_ctx* c, size_t m, const uint64_t* index, uint64_t n_leaves, const uint8_t* log, const uint8_t* nodes, uint8_t* paths,
+                    uint32_t* path_len) {
+  TRY_(merkle_refuse(egm::refuse_paths(m, n_leaves, index != nullptr, log != nullptr, nodes != nullptr, paths != nullptr, path_len != nullptr)));
+  TRY_(merkle_check_ctx(c));
+  if (m == 0) return EG_OK;
+  HIPCHK(hipSetDevice(c->device));
+  EdStage st; st.who = "merkle"; TRY_(st.open());
+  const size_t row = egm::HASH_BYTES * (size_t)egm::depth(n_leaves);
+  void *di, *dl = nullptr, *dn = nullptr, *dp = nullptr, *dlen;
+  TRY_(st.put(&di, index, m * 8));
+  if (n_leaves > 1) {
+    TRY_(st.put(&dl, log, (size_t)n_leaves * egm::HASH_BYTES));
+    TRY_(st.put(&dn, nodes, eg_merkle_nodes_bytes(n_leaves)));
+    TRY_(st.put(&dp, nullptr, m * row));
+  }
+  TRY_(st.put(&dlen, nullptr, m * 4));
+  TRY_(eg_merkle_paths_device(c, m, di, n_leaves, dl, dn, dp, dlen, st.s));
+  if (row) HIPCHK(hipMemcpyAsync(paths, dp, m * row, hipMemcpyDeviceToHost, st.s));
+  HIPCHK(hipMemcpyAsync(path_len, dlen, m * 4, hipMemcpyDeviceToHost, st.s));
+  HIPCHK(hipStreamSynchronize(st.s));
+  return EG_OK;
+}
+
+int eg_merkle_check_device(eg_ctx* c, size_t m, const void* d_index, const void* d_leaves, const void* d_paths, size_t path_stride,
+                           const void* d_path_len, uint64_t n_leaves, const void* d_root, void* d_verdict, void* d_found, void* stream) {
+  TRY_(merkle_refuse(egm::refuse_check(m, n_leaves, d_index != nullptr, d_leaves != nullptr, d_paths != nullptr, path_stride, d_path_len != nullptr,
+                                       d_root != nullptr, d_verdict != nullptr, d_found != nullptr)));
+  TRY_(merkle_check_aligned((uintptr_t)d_index, (uintptr_t)d_leaves | (uintptr_t)d_paths | (uintptr_t)d_path_len | (uintptr_t)d_root |
+                                                    (uintptr_t)d_verdict | (uintptr_t)d_found));
+  TRY_(merkle_check_ctx(c));
+  if (!d_found) return EG_OK;                                           // m == 0 and nowhere to write anything to
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)stream;
+  u32* found = static_cast<u32*>(d_found);
+  HIPCHK(hipMemsetAsync(found, 0, 3 * sizeof(u32), s));
+  if (m == 0) return EG_OK;
+  const MerkleCheckDev mem{static_cast<const unsigned long long*>(d_index), static_cast<const u32*>(d_leaves), static_cast<const u32*>(d_paths),
+                           path_stride / 4, static_cast<const u32*>(d_path_len), static_cast<const u32*>(d_root)};
+  hipLaunchKernelGGL(k_merkle_check, dim3((unsigned)((m + MERKLE_NT - 1) / MERKLE_NT)), dim3(MERKLE_NT), 0, s, mem, (uint64_t)m, n_leaves,
+                     static_cast<u32*>(d_verdict), found);
+  HIPCHK(hipGetLastError());
+  return EG_OK;
+}
+int eg_merkle_check(eg_ctx* c, size_t m, const uint64_t* index, const uint8_t* leaves, const uint8_t* paths, size_t path_stride,
+                    const uint32_t* path_len, uint64_t n_leaves, const uint8_t* root, uint32_t* verdict, uint32_t* found) {
+  TRY_(merkle_refuse(egm::refuse_check(m, n_leaves, index != nullptr, leaves != nullptr, paths != nullptr, path_stride, path_len != nullptr,
+                                       root != nullptr, verdict != nullptr, found != nullptr)));
+  TRY_(merkle_check_ctx(c));
+  if (found) found[0] = found[1] = found[2] = 0;
+  if (m == 0) return EG_OK;
+  HIPCHK(hipSetDevice(c->device));
+  EdStage st; st.who = "merkle"; TRY_(st.open());
+  void *di, *dl, *dp = nullptr, *dlen, *dr, *dv, *df;
+  TRY_(st.put(&di, index, m * 8));
+  TRY_(st.put(&dl, leaves, m * egm::HASH_BYTES));
+  if (paths) TRY_(st.put(&dp, paths, m * path_stride));
+  TRY_(st.put(&dlen, path_len, m * 4));
+  TRY_(st.put(&dr, root, egm::HASH_BYTES));
+  TRY_(st.put(&dv, nullptr, m * 4));
+  TRY_(st.put(&df, nullptr, 16));
+  TRY_(eg_merkle_check_device(c, m, di, dl, dp, path_stride, dlen, n_leaves, dr, dv, df, st.s));
+  HIPCHK(hipMemcpyAsync(verdict, dv, m * 4, hipMemcpyDeviceToHost, st.s));
+  HIPCHK(hipMemcpyAsync(found, df, 3 * sizeof(u32), hipMemcpyDeviceToHost, st.s));
+  HIPCHK(hipStreamSynchronize(st.s));
+  return EG_OK;
 }
 
 }  // extern "C"

@@ -1,7 +1,7 @@
 // voting.cpp -- the reference's examples/voting.rs on the GPU backend, in C++ on top of the C ABI:
 //   `Args::vote`            (examples/voting.rs:179-213)  ./voting [votes] [options] [seed]
 //   `Args::quadratic_vote`  (examples/voting.rs:219-269)  ./voting --qv [votes] [options] [credits] [seed]
-//   options: --devices N, --json, --precincts P, --weighted, --replays K, --signed K, --revotes K
+//   options: --devices N, --json, --precincts P, --weighted, --replays K, --signed K, --revotes K, --receipts K
 // talliers' key -> voters create ballots from their own choices -> verify every ballot -> homomorphic totals -> decrypt and
 // compare with the EXPECTED totals the voters' choices add up to.  Threshold sharing of the key (examples/voting.rs:105-120) is out
 // of scope; a single key pair stands in for the shared key (tests/test_gpu_parity.py::test_threshold_tally_end_to_end
@@ -26,6 +26,9 @@
 // voter counts) runs between weeding and the tally, reports the K first ballots as superseded and hands the voters' precincts and
 // weights to the tally from the roster (groups_out / weights_out: --precincts and --weighted combine with it); the decrypted totals
 // must equal those of the last ballots.
+// With --receipts K, after the tally, the accepted ballots are posted to the receipt log (ReceiptLog = eg_merkle_*: a Merkle tree over the
+// ballots' leaf hashes under the election's prefix); the root and the size are printed, the receipts of K accepted ballots are issued
+// and checked against the root together with one forged receipt (a flipped bit in its leaf), and the verdicts are printed.
 //
 //   g++ -std=c++17 -Iinclude examples/voting.cpp -Lelastic_elgamal_amd -leg_hip -Wl,-rpath,$PWD/elastic_elgamal_amd -o voting
 #include <cstdio>
@@ -286,10 +289,49 @@ static std::string choice_to_json(const uint8_t* b, size_t options) {
   return s;
 }
 
+// --receipts: the accepted ballots are posted to the receipt log; K receipts and one forged one are checked against the root
+static bool receipt_check(const Context& ctx, const Bytes& ballots, size_t ballot_size, const std::vector<uint32_t>& status, size_t k, uint64_t seed) {
+  const size_t n = status.size();
+  const std::string id = "election #" + std::to_string(seed);
+  const ReceiptLog receipts{ctx, Bytes(id.begin(), id.end())};
+  Bytes log;
+  const LeafPass pass = receipts.leaves(ballots, ballot_size, n, {}, status, &log);
+  const uint64_t size = log.size() / EG_MERKLE_HASH_BYTES;
+  const MerkleTree tree = receipts.tree(log);
+  printf("receipt log: %llu leaves, root ", (unsigned long long)size);
+  for (uint8_t b : tree.root) printf("%02x", b);
+  printf("\n");
+  std::vector<uint64_t> index;
+  Bytes leaves;
+  std::vector<size_t> voter;
+  for (size_t b = 0; b < n && index.size() < k; ++b) {
+    if (pass.leaf_index[b] == EG_LEAF_NONE) continue;
+    index.push_back(pass.leaf_index[b]);
+    leaves.insert(leaves.end(), pass.leaves.begin() + b * EG_MERKLE_HASH_BYTES, pass.leaves.begin() + (b + 1) * EG_MERKLE_HASH_BYTES);
+    voter.push_back(b);
+  }
+  if (index.empty()) { printf("no accepted ballot to issue a receipt for\n"); return pass.found[0] == 0; }
+  index.push_back(index[0]);                                       // the forged receipt: the first one with a flipped bit in its leaf
+  leaves.insert(leaves.end(), leaves.begin(), leaves.begin() + EG_MERKLE_HASH_BYTES);
+  leaves[leaves.size() - 1] ^= 1;
+  const Receipts issued = receipts.paths(index, log, tree.nodes);
+  const size_t stride = (size_t)ReceiptLog::depth(size) * EG_MERKLE_HASH_BYTES;
+  const ReceiptVerdicts v = receipts.check(index, leaves, issued.paths, stride, issued.path_len, size, tree.root);
+  bool ok = pass.found[0] == size && pass.found[1] == 0;
+  for (size_t j = 0; j + 1 < index.size(); ++j) {
+    printf("  receipt of voter #%zu: leaf %llu, %u path entries, %s\n", voter[j] + 1, (unsigned long long)index[j], issued.path_len[j],
+           v.verdict[j] == 0 ? "proven" : "NOT proven");
+    ok = ok && v.verdict[j] == 0;
+  }
+  const uint32_t forged = v.verdict[index.size() - 1];
+  printf("  forged receipt: %s\n", forged == EG_MERKLE_MISMATCH ? "refused (root mismatch)" : "NOT refused");
+  return ok && forged == EG_MERKLE_MISMATCH && v.found[0] == 0 && v.found[1] == 0 && v.found[2] == 1;
+}
+
 int main(int argc, char** argv) {
   bool qv = false, json = false, weighted = false;
   int devices = 1;
-  long precincts = 0, replays = 0, signed_forgeries = -1, revotes = 0;
+  long precincts = 0, replays = 0, signed_forgeries = -1, revotes = 0, receipts = -1;
   std::vector<std::string> pos;
   for (int i = 1; i < argc; ++i) {
     if (!strcmp(argv[i], "--qv")) qv = true;
@@ -300,6 +342,7 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "--replays") && i + 1 < argc) replays = atol(argv[++i]);
     else if (!strcmp(argv[i], "--signed") && i + 1 < argc) signed_forgeries = atol(argv[++i]);
     else if (!strcmp(argv[i], "--revotes") && i + 1 < argc) revotes = atol(argv[++i]);
+    else if (!strcmp(argv[i], "--receipts") && i + 1 < argc) receipts = atol(argv[++i]);
     else pos.push_back(argv[i]);
   }
   auto arg = [&](size_t k, uint64_t dflt) { return k < pos.size() ? strtoull(pos[k].c_str(), nullptr, 10) : dflt; };
@@ -313,6 +356,7 @@ int main(int argc, char** argv) {
   if (revotes < 0 || (revotes && (qv || options < 2 || (size_t)revotes * 7 > votes))) {
     printf("--revotes K is shown for choice ballots with two options or more and needs 7 K <= votes\n"); return 2;
   }
+  if (receipts < -1 || receipts > 1000000) { printf("--receipts must be in 0..1000000\n"); return 2; }
   if (precincts < 0 || precincts > (long)EG_TALLY_GROUPS_MAX) { printf("--precincts must be in 0..%u\n", EG_TALLY_GROUPS_MAX); return 2; }
 
   // one context per device slot; slot d uses GPU d when the process sees that many, else GPU 0
@@ -382,6 +426,11 @@ int main(int argc, char** argv) {
     }
     if (replays) ok = replayed_tally(ctx, group, sk, *params[0], ballots, votes, (size_t)replays, expected, votes) && ok;
     if (revotes) ok = revoted_tally(ctx, group, sk, *params[0], ballots, choices, (size_t)revotes, options, (uint32_t)precincts, weighted, seed) && ok;
+    if (receipts >= 0) {
+      std::vector<uint32_t> status(votes, 0u);
+      for (size_t i = 0; i < votes; ++i) status[i] = verdict.results[i] ? 1u : 0u;
+      ok = receipt_check(ctx, ballots, params[0]->ballot_size(), status, (size_t)receipts, seed) && ok;
+    }
   } else {
     std::vector<std::unique_ptr<QuadraticVotingParams>> params;
     for (auto& c : ctxs) params.push_back(std::make_unique<QuadraticVotingParams>(*c, pk, options, credits));
@@ -415,6 +464,11 @@ int main(int argc, char** argv) {
     if (weighted) ok = weighted_tally(ctx, group, sk, *params[0], ballots, verdict, all, options, params[0]->max_votes()) && ok;
     if (replays) ok = replayed_tally(ctx, group, sk, *params[0], ballots, votes, (size_t)replays, expected, max_votes) && ok;
     if (signed_forgeries >= 0) ok = signed_tally(ctx, group, sk, *params[0], ballots, votes, (size_t)signed_forgeries, all, options, max_votes, seed) && ok;
+    if (receipts >= 0) {
+      std::vector<uint32_t> status(votes, 0u);
+      for (size_t i = 0; i < votes; ++i) status[i] = verdict.results[i] ? 1u : 0u;
+      ok = receipt_check(ctx, ballots, params[0]->ballot_size(), status, (size_t)receipts, seed) && ok;
+    }
   }
   printf("%s: the decrypted totals %s the expected ones\n", ok ? "OK" : "MISMATCH", ok ? "equal" : "differ from");
   return ok ? 0 : 1;

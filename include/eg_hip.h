@@ -637,6 +637,100 @@ int eg_roll_check(eg_ctx*, size_t n, const uint32_t* key_index, const uint32_t* 
                   const uint64_t* roster_weights /* or NULL */, uint64_t* superseded_by, uint32_t* status_out /* or NULL */,
                   uint32_t* groups_out /* or NULL */, uint64_t* weights_out /* or NULL */, uint32_t* found /* 3 */);
 
+/* ---- receipt log: a Merkle tree over the posted ballots, built and checked on the GPU ---------------------------------------------------
+ * Every stage above decides which ballots count; none lets anyone check that a ballot which was accepted is still on the board when the
+ * tally is made.  Weeding's bulletin board is a bare array of ciphertexts: no commitment over it, nothing for a voter to hold, nothing
+ * that tells an auditor a board that silently dropped or swapped a ballot from an honest one.  Deployed systems close the gap with a hash
+ * commitment over the posted ballots (Helios and Belenios publish ballot hashes, ElectionGuard issues tracking codes, Certificate
+ * Transparency keeps the append-only log of RFC 6962).  These entries build that log, its tree, the receipts and the check of many
+ * receipts at once.
+ * ORDER IN THE CHAIN: signatures -> verify -> weed -> LEAVES -> roll -> tally.  The log is normally fed weeding's status_out: a superseded
+ * ballot stays on the board as its ciphertexts do (it was posted, and its voter holds a receipt), a copy is not posted.
+ *
+ * THE RULE.  H(x) = the first 32 bytes of SHA-512(x).  The tree is RFC 6962 2.1:
+ *   leaf_b     = H(0x00 || prefix || msg_b || extra_b)     prefix: 0..255 bytes per call (the election id, as for the signatures); msg_b:
+ *                msg_len bytes at msgs + b * msg_stride (a packed ballot buffer is passed as it is); extra_b: optionally extra_len
+ *                bytes at extra + b * extra_stride (the 64-byte signature, so that a receipt binds the signed envelope); extra == NULL
+ *                with extra_len == 0 is valid
+ *   node(l, r) = H(0x01 || l || r)
+ *   MTH of N leaves: the empty tree is H of the empty string, one leaf is its own root, otherwise node(MTH of the first k, MTH of the
+ *                rest) with k the largest power of two below N.  Equivalent, and what the kernels do: level L + 1 has ceil(n_L / 2)
+ *                nodes, node i = node(a[2i], a[2i + 1]), and an odd last node is promoted unchanged.
+ * eg_merkle_depth(N) = ceil(log2 N), 0 for N <= 1.  THE LOG is the caller's array of leaves, 32 bytes each (level 0).  THE NODE STORE
+ * holds levels 1 .. depth back to back: eg_merkle_nodes_bytes(N) bytes, level L at the byte offset and with the node count that
+ * eg_merkle_level names (level 0: offset 0 and N, the log itself).
+ * RECEIPT of leaf i in a tree of N leaves: (i, N, leaf, path), path = the audit path of RFC 6962 2.1.1: bottom-up, at each level the
+ * sibling i ^ 1 if that index exists at the level, otherwise nothing, and then i >>= 1.  Its length is a function of (i, N), at most
+ * depth(N).
+ * CHECK: the algorithm of RFC 9162 2.1.3.2.  The verdict of a receipt is a uint32, the first failure in this order wins:
+ *   0                        proven
+ *   EG_MERKLE_BAD_INDEX   1  i >= N
+ *   EG_MERKLE_BAD_LENGTH  2  path_len is not the length that (i, N) demands; no path byte is read then
+ *   EG_MERKLE_MISMATCH    3  the recomputed root differs from the given one
+ *
+ * LEAVES.  Ballot b PARTICIPATES iff status_in == NULL or status_in[b] == EG_ST_OK; bytes of other ballots are never read.
+ * leaf_index[b] (uint64) = n_prior + the rank of b among the participating ballots, EG_LEAF_NONE otherwise: the index a voter's receipt
+ * carries.  leaves_out (optional, n x 32 bytes) = the leaf of every ballot, zeroed for ballots that do not participate.  APPEND
+ * (log_count != NULL): the participating leaves are written in ballot order behind the first n_prior entries of the caller's log
+ * (log_cap x 32 bytes) and *log_count (uint64) = n_prior + appended.  If they do not fit log_cap nothing is appended, the count is
+ * n_prior and found[1] is set.  The library WRITES found[0] = the number of leaves, found[1] = non-zero if the append did not fit.
+ * TREE.  Every call is a FULL REBUILD over the N leaves of the log: root (32 bytes) and, optionally, the node store.  There is no
+ * incremental frontier state.  One launch per 10 levels: two launches up to 2^20 leaves, three above.  Without a node store the top
+ * level of every launch goes through eg_merkle_tree_scratch_bytes(N) bytes of scratch (0 up to 1024 leaves).
+ * PATHS.  For m requested leaf indices (uint64), one lane each, out of the log and the node store: paths (m x depth(N) x 32 bytes, the
+ * unused tail of a row zeroed) and path_len (uint32[m]); an index >= N gives EG_MERKLE_NO_PATH and a zeroed row.
+ * CHECK of m receipts (index, leaf, path, path_len) against a shared (N, root): receipt j's path is path_len[j] entries at paths + j *
+ * path_stride; verdict (uint32[m]) by the rule above; found[0..2] = the numbers of BAD_INDEX, BAD_LENGTH and MISMATCH verdicts.
+ * MULTI-GPU: slabs hash their leaves on their own GPUs with the global n_prior of each slab and no append; the leaves_out rows are
+ * gathered in slab order with the existing byte all-gather (distributed.gather_tallies; equal rows, so slabs are padded to the largest
+ * and leaf_index says which rows hold a leaf) and the tree is built where they land.  No new collective.
+ *
+ * TIMING: variable time throughout; the log, the receipts and the root are public data.
+ * STATELESS as weeding and the roll: the `_device` forms take device pointers and a stream, take no lock, use no workspace of the
+ * context, allocate nothing and never synchronise (`prefix` is HOST memory and is copied during the call).  The host forms do the same
+ * on host arrays, synchronous, with their own scratch; eg_merkle_leaves returns EG_ERR_BAD_ARG AFTER writing its outputs when the
+ * append did not fit.  eg_merkle_depth, eg_merkle_nodes_bytes, eg_merkle_level and the two scratch sizes are pure host functions.
+ * EG_ERR_BAD_ARG before anything is launched: NULL mandatory pointers with work to do (msgs, leaf_index, found; root, the log of a
+ * non-empty tree; index, path_len and, for N > 1, log, nodes and paths; the arrays of a check); prefix_len > 255 or a NULL prefix with a
+ * length; msg_stride < msg_len or extra_stride < extra_len; a NULL extra with a length; n, m, N or n_prior >= EG_MERKLE_LEAVES_MAX;
+ * with an append n_prior > log_cap or a NULL log; a path_stride below 32 depth(N) or no multiple of 4; a scratch that is NULL or too
+ * small; leaf, node, path, root, status, verdict and found arrays and the scratch not 4-byte aligned; 64-bit arrays (leaf_index,
+ * log_count, index) not 8-byte aligned.  Messages and extras may lie anywhere.  The argument rules come before the context is looked
+ * at.  n == 0 / m == 0 is EG_OK: the count is n_prior and the found words (where given) are zero. */
+enum { EG_MERKLE_BAD_INDEX = 1, EG_MERKLE_BAD_LENGTH = 2, EG_MERKLE_MISMATCH = 3 };   /* verdict of a receipt */
+#define EG_MERKLE_HASH_BYTES 32
+#define EG_MERKLE_LEAVES_MAX (1u << 31)
+#define EG_LEAF_NONE (~(uint64_t)0)
+#define EG_MERKLE_NO_PATH 0xffffffffu
+int eg_merkle_depth(uint64_t n_leaves);
+size_t eg_merkle_nodes_bytes(uint64_t n_leaves);
+int eg_merkle_level(uint64_t n_leaves, int level, uint64_t* offset /* bytes into the node store */, uint64_t* count /* nodes */);
+size_t eg_merkle_leaves_scratch_bytes(size_t n);
+size_t eg_merkle_tree_scratch_bytes(uint64_t n_leaves);
+int eg_merkle_leaves_device(eg_ctx*, size_t n, const void* d_msgs, size_t msg_stride, size_t msg_len, const uint8_t* prefix /* host */,
+                            size_t prefix_len, const void* d_extra /* or NULL */, size_t extra_stride, size_t extra_len,
+                            const void* d_status_in /* uint32[n] or NULL */, uint64_t n_prior, void* d_leaf_index /* uint64[n] */,
+                            void* d_leaves_out /* n x 32 or NULL */, void* d_log /* log_cap x 32, or NULL without an append */,
+                            uint64_t log_cap, void* d_log_count /* uint64, or NULL: no append */, void* d_found /* 2 x uint32 */,
+                            void* d_scratch, size_t scratch_bytes, void* stream);
+int eg_merkle_leaves(eg_ctx*, size_t n, const uint8_t* msgs, size_t msg_stride, size_t msg_len, const uint8_t* prefix, size_t prefix_len,
+                     const uint8_t* extra /* or NULL */, size_t extra_stride, size_t extra_len, const uint32_t* status_in /* or NULL */,
+                     uint64_t n_prior, uint64_t* leaf_index, uint8_t* leaves_out /* or NULL */, uint8_t* log /* log_cap x 32, or NULL */,
+                     uint64_t log_cap, uint64_t* log_count /* or NULL: no append */, uint32_t* found /* 2 */);
+int eg_merkle_tree_device(eg_ctx*, uint64_t n_leaves, const void* d_log /* n_leaves x 32 */, void* d_root /* 32 */,
+                          void* d_nodes /* eg_merkle_nodes_bytes, or NULL */, void* d_scratch /* used without d_nodes */,
+                          size_t scratch_bytes, void* stream);
+int eg_merkle_tree(eg_ctx*, uint64_t n_leaves, const uint8_t* log, uint8_t* root, uint8_t* nodes /* or NULL */);
+int eg_merkle_paths_device(eg_ctx*, size_t m, const void* d_index /* uint64[m] */, uint64_t n_leaves, const void* d_log, const void* d_nodes,
+                           void* d_paths /* m x depth x 32 */, void* d_path_len /* uint32[m] */, void* stream);
+int eg_merkle_paths(eg_ctx*, size_t m, const uint64_t* index, uint64_t n_leaves, const uint8_t* log, const uint8_t* nodes, uint8_t* paths,
+                    uint32_t* path_len);
+int eg_merkle_check_device(eg_ctx*, size_t m, const void* d_index /* uint64[m] */, const void* d_leaves /* m x 32 */, const void* d_paths,
+                           size_t path_stride, const void* d_path_len /* uint32[m] */, uint64_t n_leaves, const void* d_root /* 32 */,
+                           void* d_verdict /* uint32[m] */, void* d_found /* 3 x uint32 */, void* stream);
+int eg_merkle_check(eg_ctx*, size_t m, const uint64_t* index, const uint8_t* leaves, const uint8_t* paths, size_t path_stride,
+                    const uint32_t* path_len, uint64_t n_leaves, const uint8_t* root, uint32_t* verdict, uint32_t* found /* 3 */);
+
 /* ---- batch tier on several GPUs of ONE process (SURVEY.md 8b `device_mask`; the reference's host is one single-threaded process,
  * examples/voting.rs:179-213) -----------------------------------------------------------------------------------------------------
  * per_device[d], d < n_dev: params objects of the SAME election (same key, options, kind), each created on its own context

@@ -877,6 +877,108 @@ struct VoterRoll {
   }
 };
 
+// Receipt log: a Merkle tree (RFC 6962, H = the first 32 bytes of SHA-512) over the posted ballots (eg_hip.h, "receipt log" has the rule);
+// fed weeding's status_out.  The log is the caller's vector of 32-byte leaves; every tree() is a full rebuild, there is no frontier state.
+struct LeafPass {
+  std::vector<uint64_t> leaf_index;                           // EG_LEAF_NONE: the ballot does not participate
+  Bytes leaves;                                               // n x 32, zeroed rows for ballots that do not participate
+  uint32_t found[2] = {0, 0};                                 // the number of leaves, non-zero: the append did not fit
+};
+struct MerkleTree {
+  Bytes root;                                                 // 32 bytes
+  Bytes nodes;                                                // levels 1 .. depth back to back (ReceiptLog::level)
+};
+struct Receipts {
+  Bytes paths;                                                // m x depth(N) x 32
+  std::vector<uint32_t> path_len;                             // EG_MERKLE_NO_PATH: no such leaf
+};
+struct ReceiptVerdicts {
+  std::vector<uint32_t> verdict;                              // 0 or EG_MERKLE_BAD_INDEX / _BAD_LENGTH / _MISMATCH
+  uint32_t found[3] = {0, 0, 0};
+};
+struct ReceiptLog {
+  const Context& ctx;
+  Bytes prefix = {};                                          // the election id, 0 .. 255 bytes
+  static int depth(uint64_t n_leaves) { return eg_merkle_depth(n_leaves); }
+  static size_t nodes_bytes(uint64_t n_leaves) { return eg_merkle_nodes_bytes(n_leaves); }
+  // (byte offset into the node store, node count) of a level; level 0 is the log itself
+  static std::pair<uint64_t, uint64_t> level(uint64_t n_leaves, int lvl) {
+    uint64_t off = 0, count = 0;
+    ok(eg_merkle_level(n_leaves, lvl, &off, &count));
+    return {off, count};
+  }
+  // the leaves of n ballots of msg_len bytes (extra: n x extra_len bytes or empty, e.g. the signatures); with `log` the participating
+  // leaves are appended to it (it grows) and leaf_index counts from its old size
+  LeafPass leaves(const Bytes& msgs, size_t msg_len, size_t n, const Bytes& extra = {}, const std::vector<uint32_t>& status_in = {},
+                  Bytes* log = nullptr, uint64_t n_prior = 0) const {
+    const size_t extra_len = n && !extra.empty() ? extra.size() / n : 0;
+    if (msgs.size() != n * msg_len || extra.size() != n * extra_len || (!status_in.empty() && status_in.size() != n))
+      throw Error(EG_ERR_BAD_ARG, "n messages of msg_len bytes, n extras of one length, one status word per ballot");
+    LeafPass v;
+    v.leaf_index.resize(n); v.leaves.resize(n * EG_MERKLE_HASH_BYTES);
+    uint64_t count = 0;
+    if (log) { n_prior = log->size() / EG_MERKLE_HASH_BYTES; log->resize((n_prior + n) * EG_MERKLE_HASH_BYTES); }
+    ok(eg_merkle_leaves(ctx.raw(), n, msgs.data(), msg_len, msg_len, prefix.empty() ? nullptr : prefix.data(), prefix.size(),
+                        extra_len ? extra.data() : nullptr, extra_len, extra_len, status_in.empty() ? nullptr : status_in.data(), n_prior,
+                        v.leaf_index.data(), v.leaves.data(), log ? log->data() : nullptr, n_prior + n, log ? &count : nullptr, v.found));
+    if (log) log->resize(count * EG_MERKLE_HASH_BYTES);
+    return v;
+  }
+  MerkleTree tree(const Bytes& log, bool with_nodes = true) const {
+    const uint64_t n = log.size() / EG_MERKLE_HASH_BYTES;
+    MerkleTree t;
+    t.root.resize(EG_MERKLE_HASH_BYTES);
+    if (with_nodes) t.nodes.resize(nodes_bytes(n) ? nodes_bytes(n) : 1);
+    ok(eg_merkle_tree(ctx.raw(), n, log.data(), t.root.data(), with_nodes ? t.nodes.data() : nullptr));
+    if (with_nodes) t.nodes.resize(nodes_bytes(n));
+    return t;
+  }
+  Receipts paths(const std::vector<uint64_t>& index, const Bytes& log, const Bytes& nodes) const {
+    const uint64_t n = log.size() / EG_MERKLE_HASH_BYTES;
+    Receipts r;
+    r.paths.resize(index.size() * (size_t)depth(n) * EG_MERKLE_HASH_BYTES); r.path_len.resize(index.size());
+    ok(eg_merkle_paths(ctx.raw(), index.size(), index.data(), n, log.data(), nodes.data(), r.paths.data(), r.path_len.data()));
+    return r;
+  }
+  // m receipts (index, leaf, path_len, path at paths + j * path_stride) against (n_leaves, root)
+  ReceiptVerdicts check(const std::vector<uint64_t>& index, const Bytes& leaves, const Bytes& paths, size_t path_stride,
+                        const std::vector<uint32_t>& path_len, uint64_t n_leaves, const Bytes& root) const {
+    const size_t m = index.size();
+    if (leaves.size() != m * EG_MERKLE_HASH_BYTES || path_len.size() != m || paths.size() < m * path_stride || root.size() != EG_MERKLE_HASH_BYTES)
+      throw Error(EG_ERR_BAD_ARG, "one leaf, one path and one path_len per receipt, a root of 32 bytes");
+    ReceiptVerdicts v;
+    v.verdict.resize(m);
+    ok(eg_merkle_check(ctx.raw(), m, index.data(), leaves.data(), paths.data(), path_stride, path_len.data(), n_leaves, root.data(),
+                       v.verdict.data(), v.found));
+    return v;
+  }
+  // asynchronous device-pointer forms: no allocation, no synchronisation, no lock
+  static size_t leaves_scratch_bytes(size_t n) { return eg_merkle_leaves_scratch_bytes(n); }
+  static size_t tree_scratch_bytes(uint64_t n_leaves) { return eg_merkle_tree_scratch_bytes(n_leaves); }
+  void leaves_device(size_t n, const void* d_msgs, size_t msg_stride, size_t msg_len, const void* d_extra, size_t extra_stride, size_t extra_len,
+                     const void* d_status_in, uint64_t n_prior, void* d_leaf_index, void* d_leaves_out, void* d_log, uint64_t log_cap,
+                     void* d_log_count, void* d_found, void* d_scratch, size_t scratch_bytes, void* stream = nullptr) const {
+    ok(eg_merkle_leaves_device(ctx.raw(), n, d_msgs, msg_stride, msg_len, prefix.empty() ? nullptr : prefix.data(), prefix.size(), d_extra,
+                               extra_stride, extra_len, d_status_in, n_prior, d_leaf_index, d_leaves_out, d_log, log_cap, d_log_count, d_found,
+                               d_scratch, scratch_bytes, stream));
+  }
+  void tree_device(uint64_t n_leaves, const void* d_log, void* d_root, void* d_nodes, void* d_scratch = nullptr, size_t scratch_bytes = 0,
+                   void* stream = nullptr) const {
+    ok(eg_merkle_tree_device(ctx.raw(), n_leaves, d_log, d_root, d_nodes, d_scratch, scratch_bytes, stream));
+  }
+  void paths_device(size_t m, const void* d_index, uint64_t n_leaves, const void* d_log, const void* d_nodes, void* d_paths, void* d_path_len,
+                    void* stream = nullptr) const {
+    ok(eg_merkle_paths_device(ctx.raw(), m, d_index, n_leaves, d_log, d_nodes, d_paths, d_path_len, stream));
+  }
+  void check_device(size_t m, const void* d_index, const void* d_leaves, const void* d_paths, size_t path_stride, const void* d_path_len,
+                    uint64_t n_leaves, const void* d_root, void* d_verdict, void* d_found, void* stream = nullptr) const {
+    ok(eg_merkle_check_device(ctx.raw(), m, d_index, d_leaves, d_paths, path_stride, d_path_len, n_leaves, d_root, d_verdict, d_found, stream));
+  }
+
+ private:
+  static void ok(int rc) { if (rc != EG_OK) throw Error(rc, eg_last_error()); }
+};
+
 // ---- tally stage (examples/voting.rs:122-177) ------------------------------------------------------------------------------------
 // Params::combine_shares (sharing/mod.rs:302-325): the first `threshold` of the given (participant index, dh element) pairs ->
 // the combined decryption [x]R, or nullopt when there are too few shares.  Verify the shares first (eg_share_params_create).
