@@ -230,6 +230,13 @@ def _load() -> C.CDLL:
         "eg_merkle_paths": (C.c_int, [vp, sz, vp, C.c_uint64, cp, cp, vp, vp]),
         "eg_merkle_check_device": (C.c_int, [vp, sz, vp, vp, vp, sz, vp, C.c_uint64, vp, vp, vp, vp]),
         "eg_merkle_check": (C.c_int, [vp, sz, vp, cp, cp, sz, vp, C.c_uint64, cp, vp, vp]),
+        "eg_merkle_consistency_len": (C.c_uint32, [C.c_uint64, C.c_uint64]),
+        "eg_merkle_heads_device": (C.c_int, [vp, sz, vp, C.c_uint64, vp, vp, vp, vp, vp]),
+        "eg_merkle_heads": (C.c_int, [vp, sz, vp, C.c_uint64, cp, cp, vp, vp]),
+        "eg_merkle_consistency_device": (C.c_int, [vp, sz, vp, C.c_uint64, vp, vp, vp, vp, vp]),
+        "eg_merkle_consistency": (C.c_int, [vp, sz, vp, C.c_uint64, cp, cp, vp, vp]),
+        "eg_merkle_consistency_check_device": (C.c_int, [vp, sz, vp, vp, vp, sz, vp, C.c_uint64, vp, vp, vp, vp]),
+        "eg_merkle_consistency_check": (C.c_int, [vp, sz, vp, cp, cp, sz, vp, C.c_uint64, cp, vp, vp]),
         "eg_proof_params_create": (C.c_int, [vp, cp, C.c_int, C.c_uint64, C.POINTER(vp)]),
         "eg_share_params_create": (C.c_int, [vp, cp, C.c_uint64, C.c_uint64, C.c_uint64, cp, C.POINTER(vp)]),
         "eg_proof_params_destroy": (None, [vp]),
@@ -307,6 +314,7 @@ ROLL_SUPERSEDED, ROLL_OFF_ROLL, ROLL_NOT_CAST = 1, 2, 3
 SEQ_NONE = (1 << 64) - 1         # include/eg_hip.h: EG_SEQ_NONE
 ROLL_KEYS_MAX = 1 << 31          # include/eg_hip.h: EG_ROLL_KEYS_MAX
 MERKLE_BAD_INDEX, MERKLE_BAD_LENGTH, MERKLE_MISMATCH = 1, 2, 3    # include/eg_hip.h: EG_MERKLE_*, the verdict of a receipt
+MERKLE_MISMATCH_OLD = 4          # include/eg_hip.h: EG_MERKLE_MISMATCH_OLD, a consistency proof that does not give the old root
 MERKLE_HASH_BYTES = 32           # include/eg_hip.h: EG_MERKLE_HASH_BYTES
 MERKLE_LEAVES_MAX = 1 << 31      # include/eg_hip.h: EG_MERKLE_LEAVES_MAX
 LEAF_NONE = (1 << 64) - 1        # include/eg_hip.h: EG_LEAF_NONE, the leaf_index of a ballot that does not participate
@@ -776,6 +784,7 @@ class ReceiptLog:
     Every tree() is a full rebuild; there is no incremental frontier state."""
 
     BAD_INDEX, BAD_LENGTH, MISMATCH = MERKLE_BAD_INDEX, MERKLE_BAD_LENGTH, MERKLE_MISMATCH
+    MISMATCH_OLD = MERKLE_MISMATCH_OLD
     HASH_BYTES, LEAVES_MAX, LEAF_NONE, NO_PATH = MERKLE_HASH_BYTES, MERKLE_LEAVES_MAX, LEAF_NONE, MERKLE_NO_PATH
 
     def __init__(self, ctx: Context, prefix: bytes = b""):
@@ -888,6 +897,69 @@ class ReceiptLog:
                      d_verdict: int, d_found: int, stream: int = 0):
         _check(_load().eg_merkle_check_device(self.ctx._h, m, d_index or None, d_leaves or None, d_paths or None, path_stride, d_path_len or None,
                                               n_leaves, d_root or None, d_verdict or None, d_found or None, stream or None))
+
+    # ---- past heads and consistency proofs: "the board that published (m, R_m) is the same board, grown, that now publishes (N, R_N)"
+    @staticmethod
+    def consistency_len(old_size: int, n_leaves: int) -> int:
+        """eg_merkle_consistency_len: the length of the consistency proof of (old_size, N); NO_PATH for old_size 0 or above N."""
+        return int(_load().eg_merkle_consistency_len(old_size, n_leaves))
+
+    def heads(self, sizes, log: bytes, nodes: bytes):
+        """eg_merkle_heads: ([the head the log had at each size], found).  Size 0 gives H(""), a size above N a zeroed head, counted in
+        found[0]."""
+        n, m = len(log) // MERKLE_HASH_BYTES, len(sizes)
+        arr = (C.c_uint64 * max(m, 1))(*sizes)
+        out = C.create_string_buffer(MERKLE_HASH_BYTES * max(m, 1))
+        found = (C.c_uint32 * 1)()
+        _check(_load().eg_merkle_heads(self.ctx._h, m, arr, n, log or None, nodes or None, out, found))
+        return [out.raw[MERKLE_HASH_BYTES * j: MERKLE_HASH_BYTES * (j + 1)] for j in range(m)], list(found)
+
+    def consistency(self, old_sizes, log: bytes, nodes: bytes):
+        """eg_merkle_consistency: ([proof bytes per old size, or None for an old size that is 0 or above N], the raw rows of depth(N) + 1
+        entries, proof_len)."""
+        n, m = len(log) // MERKLE_HASH_BYTES, len(old_sizes)
+        row = MERKLE_HASH_BYTES * (self.depth(n) + 1)
+        arr = (C.c_uint64 * max(m, 1))(*old_sizes)
+        out = C.create_string_buffer(max(m * row, 1))
+        lens = (C.c_uint32 * max(m, 1))()
+        _check(_load().eg_merkle_consistency(self.ctx._h, m, arr, n, log or None, nodes or None, out, lens))
+        rows = out.raw[: m * row]
+        proofs = [None if lens[j] == MERKLE_NO_PATH else rows[j * row: j * row + MERKLE_HASH_BYTES * lens[j]] for j in range(m)]
+        return proofs, rows, list(lens[:m])
+
+    def consistency_check(self, old_sizes, old_roots, proofs, n_leaves: int, root: bytes, proof_len=None, proof_stride=None):
+        """eg_merkle_consistency_check: (verdicts, found[4]).  `old_roots` is a list of heads or their bytes back to back; `proofs` is a
+        list of proof bytes (their lengths are the proof_len), or raw rows with proof_len and proof_stride given."""
+        m = len(old_sizes)
+        if not isinstance(old_roots, (bytes, bytearray)):
+            old_roots = b"".join(old_roots)
+        if proof_len is None:
+            proof_len = [len(p) // MERKLE_HASH_BYTES for p in proofs]
+            proof_stride = max([MERKLE_HASH_BYTES * (self.depth(n_leaves) + 1)] + [len(p) for p in proofs])
+            proofs = b"".join(p + bytes(proof_stride - len(p)) for p in proofs)
+        arr = (C.c_uint64 * max(m, 1))(*old_sizes)
+        lens = (C.c_uint32 * max(m, 1))(*proof_len)
+        verdict, found = (C.c_uint32 * max(m, 1))(), (C.c_uint32 * 4)()
+        _check(_load().eg_merkle_consistency_check(self.ctx._h, m, arr, bytes(old_roots) or None, proofs or None, proof_stride, lens, n_leaves, root,
+                                                   verdict, found))
+        return list(verdict[:m]), list(found)
+
+    def heads_device(self, m: int, d_size: int, n_leaves: int, d_log: int, d_nodes: int, d_heads: int, d_found: int, stream: int = 0):
+        """Asynchronous device-pointer variant (eg_merkle_heads_device).  d_size: m uint64; d_heads: m x 32; d_found: 1 uint32."""
+        _check(_load().eg_merkle_heads_device(self.ctx._h, m, d_size or None, n_leaves, d_log or None, d_nodes or None, d_heads or None,
+                                              d_found or None, stream or None))
+
+    def consistency_device(self, m: int, d_old_size: int, n_leaves: int, d_log: int, d_nodes: int, d_proofs: int, d_proof_len: int, stream: int = 0):
+        """eg_merkle_consistency_device.  d_proofs: m rows of depth(N) + 1 entries; d_proof_len: m uint32."""
+        _check(_load().eg_merkle_consistency_device(self.ctx._h, m, d_old_size or None, n_leaves, d_log or None, d_nodes or None, d_proofs or None,
+                                                    d_proof_len or None, stream or None))
+
+    def consistency_check_device(self, m: int, d_old_size: int, d_old_root: int, d_proofs: int, proof_stride: int, d_proof_len: int, n_leaves: int,
+                                 d_root: int, d_verdict: int, d_found: int, stream: int = 0):
+        """eg_merkle_consistency_check_device.  d_found: 4 uint32 (BAD_INDEX, BAD_LENGTH, MISMATCH, MISMATCH_OLD)."""
+        _check(_load().eg_merkle_consistency_check_device(self.ctx._h, m, d_old_size or None, d_old_root or None, d_proofs or None, proof_stride,
+                                                          d_proof_len or None, n_leaves, d_root or None, d_verdict or None, d_found or None,
+                                                          stream or None))
 
 
 def prepared_point_size() -> int:

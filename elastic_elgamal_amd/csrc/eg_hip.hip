@@ -37,6 +37,7 @@
 #include "ed25519_kernels.cuh"
 #include "roll_kernels.cuh"
 #include "merkle_kernels.cuh"
+#include "merkle_audit_kernels.cuh"
 
 using namespace eg;
 
@@ -4611,6 +4612,133 @@ int eg_merkle_check(eg_ctx* c, size_t m, const uint64_t* index, const uint8_t* l
   TRY_(eg_merkle_check_device(c, m, di, dl, dp, path_stride, dlen, n_leaves, dr, dv, df, st.s));
   HIPCHK(hipMemcpyAsync(verdict, dv, m * 4, hipMemcpyDeviceToHost, st.s));
   HIPCHK(hipMemcpyAsync(found, df, 3 * sizeof(u32), hipMemcpyDeviceToHost, st.s));
+  HIPCHK(hipStreamSynchronize(st.s));
+  return EG_OK;
+}
+
+// ---- receipt log, the audit entries: past heads, consistency proofs and their check (merkle_audit_kernels.cuh), out of the node store ----
+static int merkle_audit_aligned(uintptr_t words64, uintptr_t words32) {
+  if (words64 & 7u) return fail(EG_ERR_BAD_ARG, "merkle: size and old_size must be 8-byte aligned");
+  if (words32 & 3u) return fail(EG_ERR_BAD_ARG, "merkle: log, nodes, heads, proofs, old_root, root, proof_len, verdict and found must be 4-byte aligned");
+  return EG_OK;
+}
+uint32_t eg_merkle_consistency_len(uint64_t old_size, uint64_t n_leaves) { return egm::consistency_len(old_size, n_leaves); }
+
+int eg_merkle_heads_device(eg_ctx* c, size_t m, const void* d_size, uint64_t n_leaves, const void* d_log, const void* d_nodes, void* d_heads,
+                           void* d_found, void* stream) {
+  TRY_(merkle_refuse(egm::refuse_heads(m, n_leaves, d_size != nullptr, d_log != nullptr, d_nodes != nullptr, d_heads != nullptr, d_found != nullptr)));
+  TRY_(merkle_audit_aligned((uintptr_t)d_size, (uintptr_t)d_log | (uintptr_t)d_nodes | (uintptr_t)d_heads | (uintptr_t)d_found));
+  TRY_(merkle_check_ctx(c));
+  if (!d_found) return EG_OK;                                           // m == 0 and nowhere to write anything to
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)stream;
+  u32* found = static_cast<u32*>(d_found);
+  HIPCHK(hipMemsetAsync(found, 0, sizeof(u32), s));
+  if (m == 0) return EG_OK;
+  const MerkleHeadDev mem{static_cast<const unsigned long long*>(d_size), static_cast<const u32*>(d_log), static_cast<const u32*>(d_nodes),
+                          static_cast<u32*>(d_heads)};
+  hipLaunchKernelGGL(k_merkle_heads, dim3((unsigned)((m + MERKLE_NT - 1) / MERKLE_NT)), dim3(MERKLE_NT), 0, s, mem, (uint64_t)m, n_leaves, found);
+  HIPCHK(hipGetLastError());
+  return EG_OK;
+}
+int eg_merkle_heads(eg_ctx* c, size_t m, const uint64_t* size, uint64_t n_leaves, const uint8_t* log, const uint8_t* nodes, uint8_t* heads,
+                    uint32_t* found) {
+  TRY_(merkle_refuse(egm::refuse_heads(m, n_leaves, size != nullptr, log != nullptr, nodes != nullptr, heads != nullptr, found != nullptr)));
+  TRY_(merkle_check_ctx(c));
+  if (found) found[0] = 0;
+  if (m == 0) return EG_OK;
+  HIPCHK(hipSetDevice(c->device));
+  EdStage st; st.who = "merkle"; TRY_(st.open());
+  void *ds, *dl = nullptr, *dn = nullptr, *dh, *df;
+  TRY_(st.put(&ds, size, m * 8));
+  if (n_leaves > 0) TRY_(st.put(&dl, log, (size_t)n_leaves * egm::HASH_BYTES));
+  if (n_leaves > 1) TRY_(st.put(&dn, nodes, eg_merkle_nodes_bytes(n_leaves)));
+  TRY_(st.put(&dh, nullptr, m * egm::HASH_BYTES));
+  TRY_(st.put(&df, nullptr, 16));
+  TRY_(eg_merkle_heads_device(c, m, ds, n_leaves, dl, dn, dh, df, st.s));
+  HIPCHK(hipMemcpyAsync(heads, dh, m * egm::HASH_BYTES, hipMemcpyDeviceToHost, st.s));
+  HIPCHK(hipMemcpyAsync(found, df, sizeof(u32), hipMemcpyDeviceToHost, st.s));
+  HIPCHK(hipStreamSynchronize(st.s));
+  return EG_OK;
+}
+
+int eg_merkle_consistency_device(eg_ctx* c, size_t m, const void* d_old_size, uint64_t n_leaves, const void* d_log, const void* d_nodes,
+                                 void* d_proofs, void* d_proof_len, void* stream) {
+  TRY_(merkle_refuse(egm::refuse_consistency(m, n_leaves, d_old_size != nullptr, d_log != nullptr, d_nodes != nullptr, d_proofs != nullptr,
+                                             d_proof_len != nullptr)));
+  TRY_(merkle_audit_aligned((uintptr_t)d_old_size, (uintptr_t)d_log | (uintptr_t)d_nodes | (uintptr_t)d_proofs | (uintptr_t)d_proof_len));
+  TRY_(merkle_check_ctx(c));
+  if (m == 0) return EG_OK;
+  HIPCHK(hipSetDevice(c->device));
+  const int row = (int)egm::consistency_row(n_leaves);
+  const MerkleConsDev mem{static_cast<const u32*>(d_log), static_cast<const u32*>(d_nodes), static_cast<u32*>(d_proofs), egm::HASH_WORDS * (size_t)row};
+  hipLaunchKernelGGL(k_merkle_consistency, dim3((unsigned)((m + MERKLE_NT - 1) / MERKLE_NT)), dim3(MERKLE_NT), 0, (hipStream_t)stream, mem,
+                     static_cast<const unsigned long long*>(d_old_size), (uint64_t)m, n_leaves, row, static_cast<u32*>(d_proof_len));
+  HIPCHK(hipGetLastError());
+  return EG_OK;
+}
+int eg_merkle_consistency(eg_ctx* c, size_t m, const uint64_t* old_size, uint64_t n_leaves, const uint8_t* log, const uint8_t* nodes, uint8_t* proofs,
+                          uint32_t* proof_len) {
+  TRY_(merkle_refuse(egm::refuse_consistency(m, n_leaves, old_size != nullptr, log != nullptr, nodes != nullptr, proofs != nullptr, proof_len != nullptr)));
+  TRY_(merkle_check_ctx(c));
+  if (m == 0) return EG_OK;
+  HIPCHK(hipSetDevice(c->device));
+  EdStage st; st.who = "merkle"; TRY_(st.open());
+  const size_t row = egm::HASH_BYTES * egm::consistency_row(n_leaves);
+  void *ds, *dl = nullptr, *dn = nullptr, *dp, *dlen;
+  TRY_(st.put(&ds, old_size, m * 8));
+  if (n_leaves > 0) TRY_(st.put(&dl, log, (size_t)n_leaves * egm::HASH_BYTES));
+  if (n_leaves > 1) TRY_(st.put(&dn, nodes, eg_merkle_nodes_bytes(n_leaves)));
+  TRY_(st.put(&dp, nullptr, m * row));
+  TRY_(st.put(&dlen, nullptr, m * 4));
+  TRY_(eg_merkle_consistency_device(c, m, ds, n_leaves, dl, dn, dp, dlen, st.s));
+  HIPCHK(hipMemcpyAsync(proofs, dp, m * row, hipMemcpyDeviceToHost, st.s));
+  HIPCHK(hipMemcpyAsync(proof_len, dlen, m * 4, hipMemcpyDeviceToHost, st.s));
+  HIPCHK(hipStreamSynchronize(st.s));
+  return EG_OK;
+}
+
+int eg_merkle_consistency_check_device(eg_ctx* c, size_t m, const void* d_old_size, const void* d_old_root, const void* d_proofs, size_t proof_stride,
+                                       const void* d_proof_len, uint64_t n_leaves, const void* d_root, void* d_verdict, void* d_found, void* stream) {
+  TRY_(merkle_refuse(egm::refuse_consistency_check(m, n_leaves, d_old_size != nullptr, d_old_root != nullptr, d_proofs != nullptr, proof_stride,
+                                                   d_proof_len != nullptr, d_root != nullptr, d_verdict != nullptr, d_found != nullptr)));
+  TRY_(merkle_audit_aligned((uintptr_t)d_old_size, (uintptr_t)d_old_root | (uintptr_t)d_proofs | (uintptr_t)d_proof_len | (uintptr_t)d_root |
+                                                       (uintptr_t)d_verdict | (uintptr_t)d_found));
+  TRY_(merkle_check_ctx(c));
+  if (!d_found) return EG_OK;                                           // m == 0 and nowhere to write anything to
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)stream;
+  u32* found = static_cast<u32*>(d_found);
+  HIPCHK(hipMemsetAsync(found, 0, 4 * sizeof(u32), s));
+  if (m == 0) return EG_OK;
+  const MerkleConsCheckDev mem{static_cast<const unsigned long long*>(d_old_size), static_cast<const u32*>(d_old_root),
+                               static_cast<const u32*>(d_proofs), proof_stride / 4, static_cast<const u32*>(d_proof_len),
+                               static_cast<const u32*>(d_root)};
+  hipLaunchKernelGGL(k_merkle_cons_check, dim3((unsigned)((m + MERKLE_NT - 1) / MERKLE_NT)), dim3(MERKLE_NT), 0, s, mem, (uint64_t)m, n_leaves,
+                     static_cast<u32*>(d_verdict), found);
+  HIPCHK(hipGetLastError());
+  return EG_OK;
+}
+int eg_merkle_consistency_check(eg_ctx* c, size_t m, const uint64_t* old_size, const uint8_t* old_root, const uint8_t* proofs, size_t proof_stride,
+                                const uint32_t* proof_len, uint64_t n_leaves, const uint8_t* root, uint32_t* verdict, uint32_t* found) {
+  TRY_(merkle_refuse(egm::refuse_consistency_check(m, n_leaves, old_size != nullptr, old_root != nullptr, proofs != nullptr, proof_stride,
+                                                   proof_len != nullptr, root != nullptr, verdict != nullptr, found != nullptr)));
+  TRY_(merkle_check_ctx(c));
+  if (found) found[0] = found[1] = found[2] = found[3] = 0;
+  if (m == 0) return EG_OK;
+  HIPCHK(hipSetDevice(c->device));
+  EdStage st; st.who = "merkle"; TRY_(st.open());
+  void *ds, *dor, *dp = nullptr, *dlen, *dr, *dv, *df;
+  TRY_(st.put(&ds, old_size, m * 8));
+  TRY_(st.put(&dor, old_root, m * egm::HASH_BYTES));
+  if (proofs) TRY_(st.put(&dp, proofs, m * proof_stride));
+  TRY_(st.put(&dlen, proof_len, m * 4));
+  TRY_(st.put(&dr, root, egm::HASH_BYTES));
+  TRY_(st.put(&dv, nullptr, m * 4));
+  TRY_(st.put(&df, nullptr, 16));
+  TRY_(eg_merkle_consistency_check_device(c, m, ds, dor, dp, proof_stride, dlen, n_leaves, dr, dv, df, st.s));
+  HIPCHK(hipMemcpyAsync(verdict, dv, m * 4, hipMemcpyDeviceToHost, st.s));
+  HIPCHK(hipMemcpyAsync(found, df, 4 * sizeof(u32), hipMemcpyDeviceToHost, st.s));
   HIPCHK(hipStreamSynchronize(st.s));
   return EG_OK;
 }

@@ -1,7 +1,7 @@
 // voting.cpp -- the reference's examples/voting.rs on the GPU backend, in C++ on top of the C ABI:
 //   `Args::vote`            (examples/voting.rs:179-213)  ./voting [votes] [options] [seed]
 //   `Args::quadratic_vote`  (examples/voting.rs:219-269)  ./voting --qv [votes] [options] [credits] [seed]
-//   options: --devices N, --json, --precincts P, --weighted, --replays K, --signed K, --revotes K, --receipts K
+//   options: --devices N, --json, --precincts P, --weighted, --replays K, --signed K, --revotes K, --receipts K, --heads K
 // talliers' key -> voters create ballots from their own choices -> verify every ballot -> homomorphic totals -> decrypt and
 // compare with the EXPECTED totals the voters' choices add up to.  Threshold sharing of the key (examples/voting.rs:105-120) is out
 // of scope; a single key pair stands in for the shared key (tests/test_gpu_parity.py::test_threshold_tally_end_to_end
@@ -29,6 +29,10 @@
 // With --receipts K, after the tally, the accepted ballots are posted to the receipt log (ReceiptLog = eg_merkle_*: a Merkle tree over the
 // ballots' leaf hashes under the election's prefix); the root and the size are printed, the receipts of K accepted ballots are issued
 // and checked against the root together with one forged receipt (a flipped bit in its leaf), and the verdicts are printed.
+// With --heads K (only with --receipts), K earlier sizes of the log spread over 1 .. N stand for the heads that voters and monitors were
+// given before: their heads are re-derived from the node store (heads = eg_merkle_heads), their consistency proofs against the present
+// head are issued and checked (consistency / consistency_check: the board only grew), and one old head with a flipped bit must be
+// refused as the old root's mismatch; one summary line is printed.
 //
 //   g++ -std=c++17 -Iinclude examples/voting.cpp -Lelastic_elgamal_amd -leg_hip -Wl,-rpath,$PWD/elastic_elgamal_amd -o voting
 #include <cstdio>
@@ -289,8 +293,34 @@ static std::string choice_to_json(const uint8_t* b, size_t options) {
   return s;
 }
 
+// --heads: K earlier sizes of the log spread over 1 .. N: their heads out of the node store, their consistency proofs against the present
+// head, all proven; then one old head with a flipped bit, refused as the old root's mismatch
+static bool heads_check(const ReceiptLog& receipts, const Bytes& log, const MerkleTree& tree, size_t k) {
+  const uint64_t size = log.size() / EG_MERKLE_HASH_BYTES;
+  if (size == 0 || k == 0) { printf("past heads: none to check\n"); return true; }
+  std::vector<uint64_t> old;
+  for (size_t j = 0; j < k; ++j) old.push_back(k == 1 ? size : 1 + (uint64_t)j * (size - 1) / (k - 1));
+  uint64_t bent = 0;                                               // an old size with a seed: not a power of two, below N
+  for (uint64_t m : old) if (!bent && m < size && (m & (m - 1))) bent = m;
+  if (!bent && size >= 4) bent = 3;
+  if (bent) old.push_back(bent);
+  const PastHeads past = receipts.heads(old, log, tree.nodes);
+  Bytes roots = past.heads;
+  if (bent) roots[roots.size() - 1] ^= 1;
+  const ConsistencyProofs issued = receipts.consistency(old, log, tree.nodes);
+  const size_t stride = ((size_t)ReceiptLog::depth(size) + 1) * EG_MERKLE_HASH_BYTES;
+  const ConsistencyVerdicts v = receipts.consistency_check(old, roots, issued.proofs, stride, issued.proof_len, size, tree.root);
+  size_t proven = 0, entries = 0;
+  for (size_t j = 0; j < k; ++j) { proven += v.verdict[j] == 0; entries += issued.proof_len[j]; }
+  const bool forged_ok = !bent || v.verdict[k] == EG_MERKLE_MISMATCH_OLD;
+  printf("past heads: %zu of %zu consistency proofs proven against the head of %llu leaves (%zu proof entries); forged old head: %s\n", proven, k,
+         (unsigned long long)size, entries, !bent ? "none to forge" : forged_ok ? "refused (old root mismatch)" : "NOT refused");
+  return proven == k && forged_ok && past.found[0] == 0 && v.found[0] == 0 && v.found[1] == 0 && v.found[2] == 0 && v.found[3] == (bent ? 1u : 0u);
+}
+
 // --receipts: the accepted ballots are posted to the receipt log; K receipts and one forged one are checked against the root
-static bool receipt_check(const Context& ctx, const Bytes& ballots, size_t ballot_size, const std::vector<uint32_t>& status, size_t k, uint64_t seed) {
+static bool receipt_check(const Context& ctx, const Bytes& ballots, size_t ballot_size, const std::vector<uint32_t>& status, size_t k, uint64_t seed,
+                          long heads = -1) {
   const size_t n = status.size();
   const std::string id = "election #" + std::to_string(seed);
   const ReceiptLog receipts{ctx, Bytes(id.begin(), id.end())};
@@ -310,7 +340,10 @@ static bool receipt_check(const Context& ctx, const Bytes& ballots, size_t ballo
     leaves.insert(leaves.end(), pass.leaves.begin() + b * EG_MERKLE_HASH_BYTES, pass.leaves.begin() + (b + 1) * EG_MERKLE_HASH_BYTES);
     voter.push_back(b);
   }
-  if (index.empty()) { printf("no accepted ballot to issue a receipt for\n"); return pass.found[0] == 0; }
+  if (index.empty()) {
+    printf("no accepted ballot to issue a receipt for\n");
+    return pass.found[0] == 0 && (heads < 0 || heads_check(receipts, log, tree, (size_t)heads));
+  }
   index.push_back(index[0]);                                       // the forged receipt: the first one with a flipped bit in its leaf
   leaves.insert(leaves.end(), leaves.begin(), leaves.begin() + EG_MERKLE_HASH_BYTES);
   leaves[leaves.size() - 1] ^= 1;
@@ -325,13 +358,14 @@ static bool receipt_check(const Context& ctx, const Bytes& ballots, size_t ballo
   }
   const uint32_t forged = v.verdict[index.size() - 1];
   printf("  forged receipt: %s\n", forged == EG_MERKLE_MISMATCH ? "refused (root mismatch)" : "NOT refused");
-  return ok && forged == EG_MERKLE_MISMATCH && v.found[0] == 0 && v.found[1] == 0 && v.found[2] == 1;
+  ok = ok && forged == EG_MERKLE_MISMATCH && v.found[0] == 0 && v.found[1] == 0 && v.found[2] == 1;
+  return heads < 0 ? ok : heads_check(receipts, log, tree, (size_t)heads) && ok;
 }
 
 int main(int argc, char** argv) {
   bool qv = false, json = false, weighted = false;
   int devices = 1;
-  long precincts = 0, replays = 0, signed_forgeries = -1, revotes = 0, receipts = -1;
+  long precincts = 0, replays = 0, signed_forgeries = -1, revotes = 0, receipts = -1, heads = -1;
   std::vector<std::string> pos;
   for (int i = 1; i < argc; ++i) {
     if (!strcmp(argv[i], "--qv")) qv = true;
@@ -343,6 +377,7 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "--signed") && i + 1 < argc) signed_forgeries = atol(argv[++i]);
     else if (!strcmp(argv[i], "--revotes") && i + 1 < argc) revotes = atol(argv[++i]);
     else if (!strcmp(argv[i], "--receipts") && i + 1 < argc) receipts = atol(argv[++i]);
+    else if (!strcmp(argv[i], "--heads") && i + 1 < argc) heads = atol(argv[++i]);
     else pos.push_back(argv[i]);
   }
   auto arg = [&](size_t k, uint64_t dflt) { return k < pos.size() ? strtoull(pos[k].c_str(), nullptr, 10) : dflt; };
@@ -357,6 +392,7 @@ int main(int argc, char** argv) {
     printf("--revotes K is shown for choice ballots with two options or more and needs 7 K <= votes\n"); return 2;
   }
   if (receipts < -1 || receipts > 1000000) { printf("--receipts must be in 0..1000000\n"); return 2; }
+  if (heads < -1 || heads > 1000000 || (heads >= 0 && receipts < 0)) { printf("--heads must be in 0..1000000 and needs --receipts\n"); return 2; }
   if (precincts < 0 || precincts > (long)EG_TALLY_GROUPS_MAX) { printf("--precincts must be in 0..%u\n", EG_TALLY_GROUPS_MAX); return 2; }
 
   // one context per device slot; slot d uses GPU d when the process sees that many, else GPU 0
@@ -429,7 +465,7 @@ int main(int argc, char** argv) {
     if (receipts >= 0) {
       std::vector<uint32_t> status(votes, 0u);
       for (size_t i = 0; i < votes; ++i) status[i] = verdict.results[i] ? 1u : 0u;
-      ok = receipt_check(ctx, ballots, params[0]->ballot_size(), status, (size_t)receipts, seed) && ok;
+      ok = receipt_check(ctx, ballots, params[0]->ballot_size(), status, (size_t)receipts, seed, heads) && ok;
     }
   } else {
     std::vector<std::unique_ptr<QuadraticVotingParams>> params;
@@ -467,7 +503,7 @@ int main(int argc, char** argv) {
     if (receipts >= 0) {
       std::vector<uint32_t> status(votes, 0u);
       for (size_t i = 0; i < votes; ++i) status[i] = verdict.results[i] ? 1u : 0u;
-      ok = receipt_check(ctx, ballots, params[0]->ballot_size(), status, (size_t)receipts, seed) && ok;
+      ok = receipt_check(ctx, ballots, params[0]->ballot_size(), status, (size_t)receipts, seed, heads) && ok;
     }
   }
   printf("%s: the decrypted totals %s the expected ones\n", ok ? "OK" : "MISMATCH", ok ? "equal" : "differ from");

@@ -730,6 +730,56 @@ int eg_merkle_check_device(eg_ctx*, size_t m, const void* d_index /* uint64[m] *
                            void* d_verdict /* uint32[m] */, void* d_found /* 3 x uint32 */, void* stream);
 int eg_merkle_check(eg_ctx*, size_t m, const uint64_t* index, const uint8_t* leaves, const uint8_t* paths, size_t path_stride,
                     const uint32_t* path_len, uint64_t n_leaves, const uint8_t* root, uint32_t* verdict, uint32_t* found /* 3 */);
+/* The receipt log, continued: PAST HEADS and CONSISTENCY PROOFS (RFC 6962 2.1.2, RFC 9162 2.1.4).  A receipt proves "my ballot is under
+ * root R_N"; these entries prove "the board that published (m, R_m) earlier is the same board, grown, that now publishes (N, R_N)": the
+ * holder of an old head checks it once against the new one, and every receipt that proved against R_m counts for good, with no
+ * re-issue.  Nothing is added to the tree: node j of level L of the node store is the tree hash of leaves [j 2^L, min((j + 1) 2^L, N)),
+ * the promoted ragged last node included, and every node that is needed is one of those.  R_m = MTH of the first m leaves, 1 <= m <= N.
+ * PAST HEAD.  R_0 = H("").  For m >= 1 walk the bits of m from the bottom: x = m at level L = 0; where x is odd take node (L, x - 1), a
+ * complete subtree wholly inside the first m leaves, and fold it on the left, acc = node(that, acc) (the first node taken is acc itself);
+ * then x >>= 1, L += 1.  At most depth(N) node hashes; R_N is the root.
+ * CONSISTENCY PROOF of (m, N) = PROOF(m, D[N]) of RFC 9162 2.1.4.1, read out of the store: empty for m == N; otherwise node = m - 1 at
+ * level L = 0, and while node is odd node >>= 1, L += 1.  If node != 0 the first entry is store node (L, node), THE SEED: the last
+ * complete piece of the old tree (node == 0: m is a power of two and there is no seed).  Then the audit path of node (L, node) inside
+ * the N-tree, bottom-up as for a receipt: at each level with more than one node the sibling node ^ 1 if that index exists at the level,
+ * then node >>= 1.  eg_merkle_consistency_len(m, N) is that count: 0 for m == N, at most depth(N) + 1 (reached, e.g. (3, 6) -> 4),
+ * EG_MERKLE_NO_PATH for m == 0 or m > N.
+ * CHECK of a proof: the algorithm of RFC 9162 2.1.4.2.  The verdict is a uint32, the first failure in this order wins:
+ *   0                           proven
+ *   EG_MERKLE_BAD_INDEX      1  old_size == 0 or old_size > N
+ *   EG_MERKLE_BAD_LENGTH     2  proof_len is not eg_merkle_consistency_len(old_size, N); no proof byte is read then
+ *   EG_MERKLE_MISMATCH_OLD   4  the old root recomputed from the proof differs from the given old root
+ *   EG_MERKLE_MISMATCH       3  the new root recomputed differs from the given new root
+ * With the length exact the walk is driven by (m, N) alone: fr = sr = entry 0 if there is a seed, else the given old root; at each level
+ * with an existing sibling c: if the node index is odd fr = node(c, fr) and sr = node(c, sr), otherwise sr = node(sr, c); then fr is
+ * compared with the old root and sr with the new one.  For m == N fr = sr = the given old root, so unequal roots give EG_MERKLE_MISMATCH.
+ * HEADS of m sizes (uint64) out of the log and the node store of N leaves: heads (m x 32 bytes); size 0 gives H(""), a size above N a
+ * zeroed row, counted in found[0].  CONSISTENCY of m old sizes: proofs (m x (depth(N) + 1) x 32 bytes, the unused tail of a row zeroed)
+ * and proof_len (uint32[m]); old_size 0 or above N gives EG_MERKLE_NO_PATH and a zeroed row.  CONSISTENCY_CHECK of m proofs (old_size,
+ * old_root, proof, proof_len) against a shared (N, root): proof j is proof_len[j] entries at proofs + j * proof_stride; found[0..3] = the
+ * numbers of BAD_INDEX, BAD_LENGTH, MISMATCH and MISMATCH_OLD verdicts.
+ * The contract is the one above: variable time on public data; stateless; the `_device` forms take no lock, allocate nothing and never
+ * synchronise; m == 0 is EG_OK with zeroed found words; the argument rules come before the context is looked at, EG_ERR_BAD_ARG for
+ * NULL mandatory pointers with work to do (the log may be NULL for N == 0, the nodes for N <= 1, the proofs of a check for N <= 1), m or
+ * N >= EG_MERKLE_LEAVES_MAX, a proof_stride below 32 (depth(N) + 1) or no multiple of 4, 32-bit arrays not 4-byte aligned, 64-bit
+ * arrays (size, old_size) not 8-byte aligned.  eg_merkle_consistency_len is a pure host function. */
+enum { EG_MERKLE_MISMATCH_OLD = 4 };                                                  /* verdict of a consistency proof */
+uint32_t eg_merkle_consistency_len(uint64_t old_size, uint64_t n_leaves);
+int eg_merkle_heads_device(eg_ctx*, size_t m, const void* d_size /* uint64[m] */, uint64_t n_leaves, const void* d_log, const void* d_nodes,
+                           void* d_heads /* m x 32 */, void* d_found /* 1 x uint32 */, void* stream);
+int eg_merkle_heads(eg_ctx*, size_t m, const uint64_t* size, uint64_t n_leaves, const uint8_t* log, const uint8_t* nodes, uint8_t* heads,
+                    uint32_t* found /* 1 */);
+int eg_merkle_consistency_device(eg_ctx*, size_t m, const void* d_old_size /* uint64[m] */, uint64_t n_leaves, const void* d_log,
+                                 const void* d_nodes, void* d_proofs /* m x (depth + 1) x 32 */, void* d_proof_len /* uint32[m] */,
+                                 void* stream);
+int eg_merkle_consistency(eg_ctx*, size_t m, const uint64_t* old_size, uint64_t n_leaves, const uint8_t* log, const uint8_t* nodes,
+                          uint8_t* proofs, uint32_t* proof_len);
+int eg_merkle_consistency_check_device(eg_ctx*, size_t m, const void* d_old_size /* uint64[m] */, const void* d_old_root /* m x 32 */,
+                                       const void* d_proofs, size_t proof_stride, const void* d_proof_len /* uint32[m] */, uint64_t n_leaves,
+                                       const void* d_root /* 32 */, void* d_verdict /* uint32[m] */, void* d_found /* 4 x uint32 */,
+                                       void* stream);
+int eg_merkle_consistency_check(eg_ctx*, size_t m, const uint64_t* old_size, const uint8_t* old_root, const uint8_t* proofs, size_t proof_stride,
+                                const uint32_t* proof_len, uint64_t n_leaves, const uint8_t* root, uint32_t* verdict, uint32_t* found /* 4 */);
 
 /* ---- batch tier on several GPUs of ONE process (SURVEY.md 8b `device_mask`; the reference's host is one single-threaded process,
  * examples/voting.rs:179-213) -----------------------------------------------------------------------------------------------------

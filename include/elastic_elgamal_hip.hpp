@@ -896,6 +896,18 @@ struct ReceiptVerdicts {
   std::vector<uint32_t> verdict;                              // 0 or EG_MERKLE_BAD_INDEX / _BAD_LENGTH / _MISMATCH
   uint32_t found[3] = {0, 0, 0};
 };
+struct PastHeads {
+  Bytes heads;                                                // m x 32; H("") for size 0, a zeroed row for a size above N
+  uint32_t found[1] = {0};                                    // the number of sizes above N
+};
+struct ConsistencyProofs {
+  Bytes proofs;                                               // m x (depth(N) + 1) x 32
+  std::vector<uint32_t> proof_len;                            // EG_MERKLE_NO_PATH: old size 0 or above N
+};
+struct ConsistencyVerdicts {
+  std::vector<uint32_t> verdict;                              // 0 or EG_MERKLE_BAD_INDEX / _BAD_LENGTH / _MISMATCH_OLD / _MISMATCH
+  uint32_t found[4] = {0, 0, 0, 0};                           // BAD_INDEX, BAD_LENGTH, MISMATCH, MISMATCH_OLD
+};
 struct ReceiptLog {
   const Context& ctx;
   Bytes prefix = {};                                          // the election id, 0 .. 255 bytes
@@ -973,6 +985,47 @@ struct ReceiptLog {
   void check_device(size_t m, const void* d_index, const void* d_leaves, const void* d_paths, size_t path_stride, const void* d_path_len,
                     uint64_t n_leaves, const void* d_root, void* d_verdict, void* d_found, void* stream = nullptr) const {
     ok(eg_merkle_check_device(ctx.raw(), m, d_index, d_leaves, d_paths, path_stride, d_path_len, n_leaves, d_root, d_verdict, d_found, stream));
+  }
+  // past heads and consistency proofs (eg_hip.h, "PAST HEADS and CONSISTENCY PROOFS"), out of the log and its node store
+  static uint32_t consistency_len(uint64_t old_size, uint64_t n_leaves) { return eg_merkle_consistency_len(old_size, n_leaves); }
+  PastHeads heads(const std::vector<uint64_t>& size, const Bytes& log, const Bytes& nodes) const {
+    PastHeads h;
+    h.heads.resize(size.size() * EG_MERKLE_HASH_BYTES);
+    ok(eg_merkle_heads(ctx.raw(), size.size(), size.data(), log.size() / EG_MERKLE_HASH_BYTES, log.data(), nodes.data(), h.heads.data(), h.found));
+    return h;
+  }
+  ConsistencyProofs consistency(const std::vector<uint64_t>& old_size, const Bytes& log, const Bytes& nodes) const {
+    const uint64_t n = log.size() / EG_MERKLE_HASH_BYTES;
+    ConsistencyProofs p;
+    p.proofs.resize(old_size.size() * ((size_t)depth(n) + 1) * EG_MERKLE_HASH_BYTES); p.proof_len.resize(old_size.size());
+    ok(eg_merkle_consistency(ctx.raw(), old_size.size(), old_size.data(), n, log.data(), nodes.data(), p.proofs.data(), p.proof_len.data()));
+    return p;
+  }
+  // m proofs (old_size, old_root, proof_len, proof at proofs + j * proof_stride) against (n_leaves, root)
+  ConsistencyVerdicts consistency_check(const std::vector<uint64_t>& old_size, const Bytes& old_root, const Bytes& proofs, size_t proof_stride,
+                                        const std::vector<uint32_t>& proof_len, uint64_t n_leaves, const Bytes& root) const {
+    const size_t m = old_size.size();
+    if (old_root.size() != m * EG_MERKLE_HASH_BYTES || proof_len.size() != m || proofs.size() < m * proof_stride || root.size() != EG_MERKLE_HASH_BYTES)
+      throw Error(EG_ERR_BAD_ARG, "one old root, one proof and one proof_len per old size, a root of 32 bytes");
+    ConsistencyVerdicts v;
+    v.verdict.resize(m);
+    ok(eg_merkle_consistency_check(ctx.raw(), m, old_size.data(), old_root.data(), proofs.data(), proof_stride, proof_len.data(), n_leaves,
+                                   root.data(), v.verdict.data(), v.found));
+    return v;
+  }
+  void heads_device(size_t m, const void* d_size, uint64_t n_leaves, const void* d_log, const void* d_nodes, void* d_heads, void* d_found,
+                    void* stream = nullptr) const {
+    ok(eg_merkle_heads_device(ctx.raw(), m, d_size, n_leaves, d_log, d_nodes, d_heads, d_found, stream));
+  }
+  void consistency_device(size_t m, const void* d_old_size, uint64_t n_leaves, const void* d_log, const void* d_nodes, void* d_proofs,
+                          void* d_proof_len, void* stream = nullptr) const {
+    ok(eg_merkle_consistency_device(ctx.raw(), m, d_old_size, n_leaves, d_log, d_nodes, d_proofs, d_proof_len, stream));
+  }
+  void consistency_check_device(size_t m, const void* d_old_size, const void* d_old_root, const void* d_proofs, size_t proof_stride,
+                                const void* d_proof_len, uint64_t n_leaves, const void* d_root, void* d_verdict, void* d_found,
+                                void* stream = nullptr) const {
+    ok(eg_merkle_consistency_check_device(ctx.raw(), m, d_old_size, d_old_root, d_proofs, proof_stride, d_proof_len, n_leaves, d_root, d_verdict,
+                                          d_found, stream));
   }
 
  private:
