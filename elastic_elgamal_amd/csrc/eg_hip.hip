@@ -1260,6 +1260,41 @@ struct DevBuf {      // a device buffer owned for the length of one call (batch-
   int get(void* dst, size_t bytes, hipStream_t s) { if (bytes) HIPCHK(hipMemcpyAsync(dst, p, bytes, hipMemcpyDeviceToHost, s)); return EG_OK; }
 };
 #define TRY(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
+// Host staging of the stateless passes' "host arrays in, host arrays out" entries: device buffers and a stream of the call's own, released
+// on every path.  DevBuf above and prim_bufs below stay apart: they work on the context's stream under its lock, and an allocation that
+// does not fit is EG_ERR_HIP there and EG_ERR_NOMEM here, so one helper for both would change an error code.
+struct HostStage {
+  const char* who;                                            // the entry's family: the prefix of its error texts
+  std::vector<void*> bufs;
+  hipStream_t s = nullptr;
+  explicit HostStage(const char* who_) : who(who_) {}
+  ~HostStage() {
+    for (void* p : bufs) if (p) (void)hipFree(p);
+    if (s) (void)hipStreamDestroy(s);
+  }
+  int open() { HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); return EG_OK; }
+  int put(void** out, const void* src, size_t bytes) {        // src null: room only
+    void* p = nullptr;
+    const hipError_t he = hipMalloc(&p, std::max<size_t>(bytes, 16));
+    if (he == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(EG_ERR_NOMEM, std::string(who) + ": the staging buffers do not fit the device memory"); }
+    HIPCHK(he);
+    bufs.push_back(p);
+    if (src && bytes) HIPCHK(hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, s));
+    *out = p;
+    return EG_OK;
+  }
+  int get(void* dst, const void* src, size_t bytes) { HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s)); return EG_OK; }
+  int sync() { HIPCHK(hipStreamSynchronize(s)); return EG_OK; }
+};
+// the argument rules of the stateless passes need no context (so they can be tested without a GPU); what passes them fails on a null one
+static int check_ctx(const char* who, const eg_ctx* c) { return c ? EG_OK : fail(EG_ERR_BAD_ARG, std::string(who) + ": null ctx"); }
+// device pointers of 64-bit and of 32-bit words, or-ed together; a family's two messages name its arguments of either kind
+struct AlignedMsgs { const char* words64; const char* words32; };
+static int check_aligned(const AlignedMsgs& msgs, uintptr_t words64, uintptr_t words32) {
+  if (words64 & 7u) return fail(EG_ERR_BAD_ARG, msgs.words64);
+  if (words32 & 3u) return fail(EG_ERR_BAD_ARG, msgs.words32);
+  return EG_OK;
+}
 // The primitive tier works out of ONE device scratch area per context, kept between calls (round 2 paid three to five hipMalloc /
 // hipFree per call).  Every primitive call runs under the context lock and ends with a stream synchronisation, so the area is free
 // again when the next call starts; it only ever grows.
@@ -1441,7 +1476,7 @@ static PipLayout pip_layout(size_t terms) {
   L.idx = take((size_t)L.W * terms * sizeof(u32));
   for (int l = 0; l < PIP_MAX_LEVELS; ++l) { L.pieces[l] = take(nb * sizeof(u32)); L.piece0[l] = take(nb * sizeof(u32)); }
   L.totals = take(256);
-  L.tiles = take(((nb + 1023) / 1024) * PIP_SEQ * sizeof(u32));
+  L.tiles = take((size_t)egscan::scan_tiles(nb) * PIP_SEQ * sizeof(u32));
   L.psum[0] = take(L.psum_points * PT_QUADS * sizeof(uint4));
   L.psum[1] = take(L.psum_points * PT_QUADS * sizeof(uint4));
   L.flag = take(256);
@@ -1469,7 +1504,7 @@ static int pip_launch(eg_ctx* c, size_t terms, const u32* d_scalars, const u32* 
     PipScan S;
     S.offsets = P.offsets; S.cursors = P.cursors; S.totals = totals; S.tile_sums = at(L.tiles);
     for (int l = 0; l < PIP_SEQ - 1; ++l) { S.pieces[l] = at(L.pieces[l]); S.piece0[l] = at(L.piece0[l]); }
-    const unsigned tiles = (nb + 1023u) / 1024u;
+    const unsigned tiles = egscan::scan_tiles(nb);
     hipLaunchKernelGGL(k_pip_scan_tiles, dim3(tiles), dim3(NT), 0, s, (const u32*)P.counts, nb, L.levels, S);
     hipLaunchKernelGGL(k_pip_scan_tops, dim3(1), dim3(64 * PIP_SEQ), 0, s, tiles, S);
     hipLaunchKernelGGL(k_pip_scan_apply, dim3(tiles), dim3(NT), 0, s, (const u32*)P.counts, nb, L.levels, S);
@@ -1750,33 +1785,21 @@ int eg_combine_shares_batch(eg_ctx* c, uint64_t shares, uint64_t threshold, size
   if (!c) return fail(EG_ERR_BAD_ARG, "share combine: null context");
   if (m == 0) return EG_OK;
   HIPCHK(hipSetDevice(c->device));
-  enum { CTS, ITEMS, STATUS, DH, PLAIN, COMBINED, USED, BAD, SCRATCH, N_BUF };
-  const size_t sizes[N_BUF] = {m * 64, (size_t)k * m * 128, status ? (size_t)k * m * 4 : 0, m * 32, m * 32, m, m * 8, 16,
-                               egsc::scratch_bytes(threshold, m)};
-  void* d[N_BUF] = {};
-  hipStream_t s = nullptr;
-  ScopeExit release{[&]() {
-    for (void* p : d) if (p) (void)hipFree(p);
-    if (s) (void)hipStreamDestroy(s);
-  }};
-  for (int b = 0; b < N_BUF; ++b) {
-    const hipError_t he = hipMalloc(&d[b], std::max<size_t>(sizes[b], 16));
-    if (he == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(EG_ERR_NOMEM, "share combine: the staging buffers do not fit the device memory"); }
-    HIPCHK(he);
-  }
-  HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-  HIPCHK(hipMemcpyAsync(d[CTS], ciphertexts, sizes[CTS], hipMemcpyHostToDevice, s));
-  if (k) HIPCHK(hipMemcpyAsync(d[ITEMS], items, sizes[ITEMS], hipMemcpyHostToDevice, s));
-  if (k && status) HIPCHK(hipMemcpyAsync(d[STATUS], status, sizes[STATUS], hipMemcpyHostToDevice, s));
-  TRY_(eg_combine_shares_batch_device(c, shares, threshold, m, d[CTS], k, indexes, d[ITEMS], status ? d[STATUS] : nullptr, d[DH], d[PLAIN],
-                                      d[COMBINED], d[USED], d[BAD], d[SCRATCH], s));
+  HostStage st("share combine"); TRY_(st.open());
+  void *dct, *dit, *dst = nullptr, *ddh, *dpl, *dco, *dus, *dbad, *scratch;
+  TRY_(st.put(&dct, ciphertexts, m * 64));
+  TRY_(st.put(&dit, items, (size_t)k * m * 128));
+  if (status) TRY_(st.put(&dst, status, (size_t)k * m * 4));
+  TRY_(st.put(&ddh, nullptr, m * 32)); TRY_(st.put(&dpl, nullptr, m * 32)); TRY_(st.put(&dco, nullptr, m)); TRY_(st.put(&dus, nullptr, m * 8));
+  TRY_(st.put(&dbad, nullptr, 16)); TRY_(st.put(&scratch, nullptr, egsc::scratch_bytes(threshold, m)));
+  TRY_(eg_combine_shares_batch_device(c, shares, threshold, m, dct, k, indexes, dit, dst, ddh, dpl, dco, dus, dbad, scratch, st.s));
   u32 bad[3] = {0, 0, 0};
-  if (dh) HIPCHK(hipMemcpyAsync(dh, d[DH], sizes[DH], hipMemcpyDeviceToHost, s));
-  if (plain) HIPCHK(hipMemcpyAsync(plain, d[PLAIN], sizes[PLAIN], hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(combined, d[COMBINED], sizes[COMBINED], hipMemcpyDeviceToHost, s));
-  if (used) HIPCHK(hipMemcpyAsync(used, d[USED], sizes[USED], hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(bad, d[BAD], sizeof bad, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
+  if (dh) TRY_(st.get(dh, ddh, m * 32));
+  if (plain) TRY_(st.get(plain, dpl, m * 32));
+  TRY_(st.get(combined, dco, m));
+  if (used) TRY_(st.get(used, dus, m * 8));
+  TRY_(st.get(bad, dbad, sizeof bad));
+  TRY_(st.sync());
   if (bad[0] || bad[1] || bad[2])
     return fail(EG_ERR_BAD_ARG, "share combine: " + std::to_string(bad[0]) + " accepted share(s) proven for another ciphertext, " +
                                     std::to_string(bad[1]) + " chosen share(s) that do not decode, " + std::to_string(bad[2]) +
@@ -2120,32 +2143,20 @@ static int grouped_host(Engine* e, size_t n, const uint8_t* ballots, const uint3
   if (!tallies || (n && (!ballots || !status || !groups))) return fail(EG_ERR_BAD_ARG, "grouped tally: null pointer");
   HIPCHK(hipSetDevice(e->ctx->device));
   const size_t T = e->plan.tally_slots.size(), stride = e->plan.stride;
-  const size_t sizes[6] = {n * stride, n * 4, n * 4, grouped_scratch_bytes(e, n, n_groups), (size_t)n_groups * T * 32, (size_t)n_groups * 4 + 8};
-  void* d[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  hipStream_t s = nullptr;
-  ScopeExit release{[&]() {
-    for (void* p : d) if (p) (void)hipFree(p);
-    if (s) (void)hipStreamDestroy(s);
-  }};
-  for (int k = 0; k < 6; ++k) {
-    const hipError_t he = hipMalloc(&d[k], std::max<size_t>(sizes[k], 16));
-    if (he == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(EG_ERR_NOMEM, "grouped tally: the staging buffers do not fit the device memory"); }
-    HIPCHK(he);
-  }
-  HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-  if (n) {
-    HIPCHK(hipMemcpyAsync(d[0], ballots, sizes[0], hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d[1], status, sizes[1], hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d[2], groups, sizes[2], hipMemcpyHostToDevice, s));
-  }
-  u32* d_counts = static_cast<u32*>(d[5]);
+  HostStage st("grouped tally"); TRY_(st.open());
+  void *db, *dst, *dg, *scratch, *dt, *dc;
+  TRY_(st.put(&db, ballots, n * stride)); TRY_(st.put(&dst, status, n * 4)); TRY_(st.put(&dg, groups, n * 4));
+  TRY_(st.put(&scratch, nullptr, grouped_scratch_bytes(e, n, n_groups)));
+  TRY_(st.put(&dt, nullptr, (size_t)n_groups * T * 32));
+  TRY_(st.put(&dc, nullptr, (size_t)n_groups * 4 + 8));                   // the counts, then the two bad counters
+  u32* d_counts = static_cast<u32*>(dc);
   u32* d_bad = d_counts + n_groups;
-  TRY_(grouped_launch(e, n, d[0], d[1], d[2], n_groups, d[3], d[4], d_counts, d_bad, s));
+  TRY_(grouped_launch(e, n, db, dst, dg, n_groups, scratch, dt, d_counts, d_bad, st.s));
   u32 bad[2] = {0, 0};
-  HIPCHK(hipMemcpyAsync(tallies, d[4], sizes[4], hipMemcpyDeviceToHost, s));
-  if (counts) HIPCHK(hipMemcpyAsync(counts, d_counts, (size_t)n_groups * 4, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(bad, d_bad, 8, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
+  TRY_(st.get(tallies, dt, (size_t)n_groups * T * 32));
+  if (counts) TRY_(st.get(counts, d_counts, (size_t)n_groups * 4));
+  TRY_(st.get(bad, d_bad, sizeof bad));
+  TRY_(st.sync());
   if (bad[0] || bad[1])
     return fail(EG_ERR_BAD_ARG, "grouped tally: " + std::to_string(bad[0]) + " accepted ballot(s) with a group id out of range, " +
                                     std::to_string(bad[1]) + " tally point(s) of accepted ballots that do not decode: discard the tallies");
@@ -2253,37 +2264,23 @@ static int weighted_host(Engine* e, size_t n, const uint8_t* ballots, const uint
   if (!tallies || (n && (!ballots || !status))) return fail(EG_ERR_BAD_ARG, "weighted tally: null pointer");
   HIPCHK(hipSetDevice(e->ctx->device));
   const size_t T = e->plan.tally_slots.size(), stride = e->plan.stride;
-  enum { BALLOTS, STATUS, WEIGHTS, GROUPS, SCRATCH, TALLIES, SUMS, COUNTS, N_BUF };
-  const size_t sizes[N_BUF] = {n * stride, n * 4, n * 8, groups ? n * 4 : 0, weighted_scratch_bytes(e, n, n_groups), (size_t)n_groups * T * 32,
-                               (size_t)n_groups * 16, (size_t)n_groups * 4 + 12};
-  void* d[N_BUF] = {};
-  hipStream_t s = nullptr;
-  ScopeExit release{[&]() {
-    for (void* p : d) if (p) (void)hipFree(p);
-    if (s) (void)hipStreamDestroy(s);
-  }};
-  for (int k = 0; k < N_BUF; ++k) {
-    const hipError_t he = hipMalloc(&d[k], std::max<size_t>(sizes[k], 16));
-    if (he == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(EG_ERR_NOMEM, "weighted tally: the staging buffers do not fit the device memory"); }
-    HIPCHK(he);
-  }
-  HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-  if (n) {
-    HIPCHK(hipMemcpyAsync(d[BALLOTS], ballots, sizes[BALLOTS], hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d[STATUS], status, sizes[STATUS], hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d[WEIGHTS], weights, sizes[WEIGHTS], hipMemcpyHostToDevice, s));
-    if (groups) HIPCHK(hipMemcpyAsync(d[GROUPS], groups, sizes[GROUPS], hipMemcpyHostToDevice, s));
-  }
-  u32* d_counts = static_cast<u32*>(d[COUNTS]);
+  HostStage st("weighted tally"); TRY_(st.open());
+  void *db, *dst, *dw, *dg = nullptr, *scratch, *dt, *dsum, *dc;
+  TRY_(st.put(&db, ballots, n * stride)); TRY_(st.put(&dst, status, n * 4)); TRY_(st.put(&dw, weights, n * 8));
+  if (groups) TRY_(st.put(&dg, groups, n * 4));
+  TRY_(st.put(&scratch, nullptr, weighted_scratch_bytes(e, n, n_groups)));
+  TRY_(st.put(&dt, nullptr, (size_t)n_groups * T * 32));
+  TRY_(st.put(&dsum, nullptr, (size_t)n_groups * 16));
+  TRY_(st.put(&dc, nullptr, (size_t)n_groups * 4 + 12));                  // the counts, then the three bad counters
+  u32* d_counts = static_cast<u32*>(dc);
   u32* d_bad = d_counts + n_groups;
-  TRY_(weighted_launch(e, n, d[BALLOTS], d[STATUS], d[WEIGHTS], weight_bits, groups ? d[GROUPS] : nullptr, n_groups, d[SCRATCH], d[TALLIES],
-                       d[SUMS], d_counts, d_bad, s));
+  TRY_(weighted_launch(e, n, db, dst, dw, weight_bits, dg, n_groups, scratch, dt, dsum, d_counts, d_bad, st.s));
   u32 bad[3] = {0, 0, 0};
-  HIPCHK(hipMemcpyAsync(tallies, d[TALLIES], sizes[TALLIES], hipMemcpyDeviceToHost, s));
-  if (weight_sums) HIPCHK(hipMemcpyAsync(weight_sums, d[SUMS], sizes[SUMS], hipMemcpyDeviceToHost, s));
-  if (counts) HIPCHK(hipMemcpyAsync(counts, d_counts, (size_t)n_groups * 4, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
+  TRY_(st.get(tallies, dt, (size_t)n_groups * T * 32));
+  if (weight_sums) TRY_(st.get(weight_sums, dsum, (size_t)n_groups * 16));
+  if (counts) TRY_(st.get(counts, d_counts, (size_t)n_groups * 4));
+  TRY_(st.get(bad, d_bad, sizeof bad));
+  TRY_(st.sync());
   if (bad[0] || bad[1] || bad[2])
     return fail(EG_ERR_BAD_ARG, "weighted tally: " + std::to_string(bad[0]) + " accepted ballot(s) with a group id out of range, " +
                                     std::to_string(bad[1]) + " tally point(s) of accepted ballots that do not decode, " + std::to_string(bad[2]) +
@@ -2391,39 +2388,30 @@ static int weed_host(Engine* e, size_t n, const uint8_t* ballots, const uint32_t
   HIPCHK(hipSetDevice(e->ctx->device));
   const size_t K = weed_keys_per_ballot(e), stride = e->plan.stride;
   const size_t board_cap = n_prior + (appended ? n * K : 0);
-  enum { BALLOTS, STATUS, BOARD, SCRATCH, DUP, OUT, N_BUF };
-  const size_t sizes[N_BUF] = {n * stride, status ? n * 4 : 0, board_cap * egw::KEY_BYTES, weed_scratch_bytes(e, n, n_prior), n * 4,
-                               n * 4 + 32};          // OUT: status_out, then (8-byte aligned) the board count and the three counters
-  void* d[N_BUF] = {};
-  hipStream_t s = nullptr;
-  ScopeExit release{[&]() {
-    for (void* p : d) if (p) (void)hipFree(p);
-    if (s) (void)hipStreamDestroy(s);
-  }};
-  for (int k = 0; k < N_BUF; ++k) {
-    const hipError_t he = hipMalloc(&d[k], std::max<size_t>(sizes[k], 16));
-    if (he == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(EG_ERR_NOMEM, "weed: the staging buffers do not fit the device memory"); }
-    HIPCHK(he);
-  }
-  HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-  if (n) HIPCHK(hipMemcpyAsync(d[BALLOTS], ballots, sizes[BALLOTS], hipMemcpyHostToDevice, s));
-  if (n && status) HIPCHK(hipMemcpyAsync(d[STATUS], status, sizes[STATUS], hipMemcpyHostToDevice, s));
-  if (n_prior) HIPCHK(hipMemcpyAsync(d[BOARD], board, n_prior * egw::KEY_BYTES, hipMemcpyHostToDevice, s));
-  char* tail = static_cast<char*>(d[OUT]) + (n * 4 + 7) / 8 * 8;
+  HostStage st("weed"); TRY_(st.open());
+  void *db, *dst = nullptr, *dboard, *scratch, *ddup, *dout;
+  TRY_(st.put(&db, ballots, n * stride));
+  if (status) TRY_(st.put(&dst, status, n * 4));
+  TRY_(st.put(&dboard, nullptr, board_cap * egw::KEY_BYTES));             // room for the appended keys behind the caller's n_prior entries
+  if (n_prior) HIPCHK(hipMemcpyAsync(dboard, board, n_prior * egw::KEY_BYTES, hipMemcpyHostToDevice, st.s));
+  TRY_(st.put(&scratch, nullptr, weed_scratch_bytes(e, n, n_prior)));
+  TRY_(st.put(&ddup, nullptr, n * 4));
+  TRY_(st.put(&dout, nullptr, n * 4 + 32));           // status_out, then (8-byte aligned) the board count and the three counters
+  char* tail = static_cast<char*>(dout) + (n * 4 + 7) / 8 * 8;
   unsigned long long* d_count = reinterpret_cast<unsigned long long*>(tail);
   u32* d_found = reinterpret_cast<u32*>(tail + 8);
-  TRY_(weed_launch(e, n, d[BALLOTS], status ? d[STATUS] : nullptr, n_prior, d[BOARD], board_cap, weed_draw_seed(), d[SCRATCH], d[DUP],
-                   status_out ? d[OUT] : nullptr, appended ? d_count : nullptr, d_found, s));
+  TRY_(weed_launch(e, n, db, dst, n_prior, dboard, board_cap, weed_draw_seed(), scratch, ddup, status_out ? dout : nullptr,
+                   appended ? d_count : nullptr, d_found, st.s));
   u32 found[3] = {0, 0, 0};
   unsigned long long count = n_prior;
-  if (n) HIPCHK(hipMemcpyAsync(dup_of, d[DUP], n * 4, hipMemcpyDeviceToHost, s));
-  if (n && status_out) HIPCHK(hipMemcpyAsync(status_out, d[OUT], n * 4, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(found, d_found, sizeof found, hipMemcpyDeviceToHost, s));
-  if (appended) HIPCHK(hipMemcpyAsync(&count, d_count, sizeof count, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
+  if (n) TRY_(st.get(dup_of, ddup, n * 4));
+  if (n && status_out) TRY_(st.get(status_out, dout, n * 4));
+  TRY_(st.get(found, d_found, sizeof found));
+  if (appended) TRY_(st.get(&count, d_count, sizeof count));
+  TRY_(st.sync());
   if (appended && count > n_prior && count <= board_cap) {
-    HIPCHK(hipMemcpyAsync(appended, static_cast<char*>(d[BOARD]) + n_prior * egw::KEY_BYTES, (count - n_prior) * egw::KEY_BYTES, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
+    TRY_(st.get(appended, static_cast<char*>(dboard) + n_prior * egw::KEY_BYTES, (count - n_prior) * egw::KEY_BYTES));
+    TRY_(st.sync());
     *n_appended = (size_t)(count - n_prior);
   }
   if (found[2]) return fail(EG_ERR_BAD_ARG, "weed: the table overflowed or the board has no room (" + std::to_string(found[2]) + "): discard the results");
@@ -4049,7 +4037,6 @@ static int ed_check_messages(size_t n, const void* msgs, size_t msg_stride, size
     return fail(EG_ERR_BAD_ARG, std::string("ed25519: ") + why);
   return EG_OK;
 }
-static int ed_check_ctx(const eg_ctx* c) { return c ? EG_OK : fail(EG_ERR_BAD_ARG, "ed25519: null ctx"); }
 static int ed_check_roster(size_t n, const void* keys, size_t n_keys, const void* key_index, const void* sigs, const void* status_out) {
   if (n && (!keys || !sigs || !status_out)) return fail(EG_ERR_BAD_ARG, "ed25519: null keys, sigs or status_out");
   if (const char* why = eged::refuse_roster(n, n_keys, key_index != nullptr)) return fail(EG_ERR_BAD_ARG, std::string("ed25519: ") + why);
@@ -4065,7 +4052,7 @@ int eg_ed25519_verify_device(eg_ctx* c, size_t n, const void* d_msgs, size_t msg
   TRY_(ed_check_roster(n, d_keys, n_keys, d_key_index, d_sigs, d_status_out));
   if (((uintptr_t)d_keys | (uintptr_t)d_sigs | (uintptr_t)d_key_index | (uintptr_t)d_status_in | (uintptr_t)d_status_out) & 3u)
     return fail(EG_ERR_BAD_ARG, "ed25519: keys, sigs, key_index and the status arrays must be 4-byte aligned");
-  TRY_(ed_check_ctx(c));
+  TRY_(check_ctx("ed25519", c));
   if (n == 0) return EG_OK;
   const eged::Layout L = eged::layout(n, (unsigned)c->cus);
   if (!d_scratch || scratch_bytes < L.total) return fail(EG_ERR_BAD_ARG, "ed25519: scratch is null or too small (eg_ed25519_verify_scratch_bytes says how much)");
@@ -4084,37 +4071,16 @@ int eg_ed25519_verify_device(eg_ctx* c, size_t n, const void* d_msgs, size_t msg
   HIPCHK(hipGetLastError());
   return EG_OK;
 }
-// host staging of the Ed25519 entries: device buffers and a stream of the call's own
-struct EdStage {
-  std::vector<void*> bufs;
-  hipStream_t s = nullptr;
-  const char* who = "ed25519";
-  ~EdStage() {
-    for (void* p : bufs) if (p) (void)hipFree(p);
-    if (s) (void)hipStreamDestroy(s);
-  }
-  int open() { HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); return EG_OK; }
-  int put(void** out, const void* src, size_t bytes) {        // src null: room only
-    void* p = nullptr;
-    const hipError_t he = hipMalloc(&p, std::max<size_t>(bytes, 16));
-    if (he == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(EG_ERR_NOMEM, std::string(who) + ": the staging buffers do not fit the device memory"); }
-    HIPCHK(he);
-    bufs.push_back(p);
-    if (src && bytes) HIPCHK(hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, s));
-    *out = p;
-    return EG_OK;
-  }
-};
 static size_t ed_msgs_bytes(size_t n, size_t msg_stride, size_t msg_len) { return n ? (n - 1) * msg_stride + msg_len : 0; }
 int eg_ed25519_verify_batch(eg_ctx* c, size_t n, const uint8_t* msgs, size_t msg_stride, size_t msg_len, const uint8_t* prefix, size_t prefix_len,
                             const uint8_t* keys, size_t n_keys, const uint32_t* key_index, const uint8_t* sigs, const uint32_t* status_in,
                             uint32_t* status_out) {
   TRY_(ed_check_messages(n, msgs, msg_stride, msg_len, prefix, prefix_len));
   TRY_(ed_check_roster(n, keys, n_keys, key_index, sigs, status_out));
-  TRY_(ed_check_ctx(c));
+  TRY_(check_ctx("ed25519", c));
   if (n == 0) return EG_OK;
   HIPCHK(hipSetDevice(c->device));
-  EdStage st; TRY_(st.open());
+  HostStage st("ed25519"); TRY_(st.open());
   const size_t need = eg_ed25519_verify_scratch_bytes(c, n);
   void *dm, *dk, *di = nullptr, *ds, *dsi = nullptr, *dso, *scratch;
   TRY_(st.put(&dm, msgs, ed_msgs_bytes(n, msg_stride, msg_len)));
@@ -4125,14 +4091,14 @@ int eg_ed25519_verify_batch(eg_ctx* c, size_t n, const uint8_t* msgs, size_t msg
   TRY_(st.put(&dso, nullptr, n * 4));
   TRY_(st.put(&scratch, nullptr, need));
   TRY_(eg_ed25519_verify_device(c, n, dm, msg_stride, msg_len, prefix, prefix_len, dk, n_keys, di, ds, dsi, dso, scratch, need, st.s));
-  HIPCHK(hipMemcpyAsync(status_out, dso, n * 4, hipMemcpyDeviceToHost, st.s));
-  HIPCHK(hipStreamSynchronize(st.s));
+  TRY_(st.get(status_out, dso, n * 4));
+  TRY_(st.sync());
   return EG_OK;
 }
 int eg_ed25519_keypair_batch_device(eg_ctx* c, size_t n, const void* d_seeds, void* d_keys, void* stream) {
   if (n >= eged::N_LIMIT) return fail(EG_ERR_BAD_ARG, "ed25519: n is 2^31 or more");
   if ((n && (!d_seeds || !d_keys)) || ((uintptr_t)d_keys & 3u)) return fail(EG_ERR_BAD_ARG, "ed25519: null seeds or keys, or keys not 4-byte aligned");
-  TRY_(ed_check_ctx(c));
+  TRY_(check_ctx("ed25519", c));
   if (n == 0) return EG_OK;
   HIPCHK(hipSetDevice(c->device));
   hipLaunchKernelGGL(k_ed25519_keypair, dim3(blocks_of(n)), dim3(NT), 0, (hipStream_t)stream, n, static_cast<const unsigned char*>(d_seeds),
@@ -4143,22 +4109,22 @@ int eg_ed25519_keypair_batch_device(eg_ctx* c, size_t n, const void* d_seeds, vo
 int eg_ed25519_keypair_batch(eg_ctx* c, size_t n, const uint8_t* seeds, uint8_t* keys) {
   if (n >= eged::N_LIMIT) return fail(EG_ERR_BAD_ARG, "ed25519: n is 2^31 or more");
   if (n && (!seeds || !keys)) return fail(EG_ERR_BAD_ARG, "ed25519: null seeds or keys");
-  TRY_(ed_check_ctx(c));
+  TRY_(check_ctx("ed25519", c));
   if (n == 0) return EG_OK;
   HIPCHK(hipSetDevice(c->device));
-  EdStage st; TRY_(st.open());
+  HostStage st("ed25519"); TRY_(st.open());
   void *dse, *dk;
   TRY_(st.put(&dse, seeds, n * 32)); TRY_(st.put(&dk, nullptr, n * 32));
   TRY_(eg_ed25519_keypair_batch_device(c, n, dse, dk, st.s));
-  HIPCHK(hipMemcpyAsync(keys, dk, n * 32, hipMemcpyDeviceToHost, st.s));
-  HIPCHK(hipStreamSynchronize(st.s));
+  TRY_(st.get(keys, dk, n * 32));
+  TRY_(st.sync());
   return EG_OK;
 }
 int eg_ed25519_sign_batch_device(eg_ctx* c, size_t n, const void* d_seeds, const void* d_msgs, size_t msg_stride, size_t msg_len,
                                  const void* d_prefix, size_t prefix_len, void* d_sigs, void* stream) {
   TRY_(ed_check_messages(n, d_msgs, msg_stride, msg_len, d_prefix, prefix_len));
   if ((n && (!d_seeds || !d_sigs)) || ((uintptr_t)d_sigs & 3u)) return fail(EG_ERR_BAD_ARG, "ed25519: null seeds or sigs, or sigs not 4-byte aligned");
-  TRY_(ed_check_ctx(c));
+  TRY_(check_ctx("ed25519", c));
   if (n == 0) return EG_OK;
   HIPCHK(hipSetDevice(c->device));
   const EdItems it{static_cast<const unsigned char*>(d_msgs), msg_stride, msg_len, static_cast<const unsigned char*>(d_prefix), prefix_len};
@@ -4171,23 +4137,23 @@ int eg_ed25519_sign_batch(eg_ctx* c, size_t n, const uint8_t* seeds, const uint8
                           size_t prefix_len, uint8_t* sigs) {
   TRY_(ed_check_messages(n, msgs, msg_stride, msg_len, prefix, prefix_len));
   if (n && (!seeds || !sigs)) return fail(EG_ERR_BAD_ARG, "ed25519: null seeds or sigs");
-  TRY_(ed_check_ctx(c));
+  TRY_(check_ctx("ed25519", c));
   if (n == 0) return EG_OK;
   HIPCHK(hipSetDevice(c->device));
-  EdStage st; TRY_(st.open());
+  HostStage st("ed25519"); TRY_(st.open());
   void *dse, *dm, *dp, *dsg;
   TRY_(st.put(&dse, seeds, n * 32)); TRY_(st.put(&dm, msgs, ed_msgs_bytes(n, msg_stride, msg_len)));
   TRY_(st.put(&dp, prefix, prefix_len)); TRY_(st.put(&dsg, nullptr, n * 64));
   TRY_(eg_ed25519_sign_batch_device(c, n, dse, dm, msg_stride, msg_len, dp, prefix_len, dsg, st.s));
-  HIPCHK(hipMemcpyAsync(sigs, dsg, n * 64, hipMemcpyDeviceToHost, st.s));
-  HIPCHK(hipStreamSynchronize(st.s));
+  TRY_(st.get(sigs, dsg, n * 64));
+  TRY_(st.sync());
   return EG_OK;
 }
 int eg_sha512_batch_device(eg_ctx* c, size_t n, const void* d_msgs, size_t msg_stride, size_t msg_len, const void* d_prefix, size_t prefix_len,
                            void* d_digests, void* stream) {
   TRY_(ed_check_messages(n, d_msgs, msg_stride, msg_len, d_prefix, prefix_len));
   if ((n && !d_digests) || ((uintptr_t)d_digests & 3u)) return fail(EG_ERR_BAD_ARG, "sha512: digests null or not 4-byte aligned");
-  TRY_(ed_check_ctx(c));
+  TRY_(check_ctx("ed25519", c));
   if (n == 0) return EG_OK;
   HIPCHK(hipSetDevice(c->device));
   const EdItems it{static_cast<const unsigned char*>(d_msgs), msg_stride, msg_len, static_cast<const unsigned char*>(d_prefix), prefix_len};
@@ -4199,15 +4165,15 @@ int eg_sha512_batch(eg_ctx* c, size_t n, const uint8_t* msgs, size_t msg_stride,
                     uint8_t* digests) {
   TRY_(ed_check_messages(n, msgs, msg_stride, msg_len, prefix, prefix_len));
   if (n && !digests) return fail(EG_ERR_BAD_ARG, "sha512: null digests");
-  TRY_(ed_check_ctx(c));
+  TRY_(check_ctx("ed25519", c));
   if (n == 0) return EG_OK;
   HIPCHK(hipSetDevice(c->device));
-  EdStage st; TRY_(st.open());
+  HostStage st("ed25519"); TRY_(st.open());
   void *dm, *dp, *dd;
   TRY_(st.put(&dm, msgs, ed_msgs_bytes(n, msg_stride, msg_len))); TRY_(st.put(&dp, prefix, prefix_len)); TRY_(st.put(&dd, nullptr, n * 64));
   TRY_(eg_sha512_batch_device(c, n, dm, msg_stride, msg_len, dp, prefix_len, dd, st.s));
-  HIPCHK(hipMemcpyAsync(digests, dd, n * 64, hipMemcpyDeviceToHost, st.s));
-  HIPCHK(hipStreamSynchronize(st.s));
+  TRY_(st.get(digests, dd, n * 64));
+  TRY_(st.sync());
   return EG_OK;
 }
 
@@ -4218,12 +4184,8 @@ static int roll_check_args(size_t n, size_t n_keys, uint64_t seq_base, int polic
   if (const char* why = egr::refuse(n, n_keys, seq_base, policy, h)) return fail(EG_ERR_BAD_ARG, std::string("roll: ") + why);
   return EG_OK;
 }
-static int roll_check_ctx(const eg_ctx* c) { return c ? EG_OK : fail(EG_ERR_BAD_ARG, "roll: null ctx"); }
-static int roll_check_aligned(uintptr_t words64, uintptr_t words32) {
-  if (words64 & 7u) return fail(EG_ERR_BAD_ARG, "roll: roll, roster_weights, superseded_by, weights_out, displaced and displaced_count must be 8-byte aligned");
-  if (words32 & 3u) return fail(EG_ERR_BAD_ARG, "roll: key_index, the status arrays, roster_groups, groups_out, found and scratch must be 4-byte aligned");
-  return EG_OK;
-}
+static const AlignedMsgs ROLL_ALIGNED{"roll: roll, roster_weights, superseded_by, weights_out, displaced and displaced_count must be 8-byte aligned",
+                                      "roll: key_index, the status arrays, roster_groups, groups_out, found and scratch must be 4-byte aligned"};
 size_t eg_roll_cast_scratch_bytes(const eg_ctx* c, size_t n, size_t n_keys) {
   return c && !egr::refuse_sizes(n, n_keys) ? egr::layout(n, n_keys).total : 0;
 }
@@ -4235,14 +4197,15 @@ int eg_roll_cast_device(eg_ctx* c, size_t n, const void* d_key_index, const void
                        egr::Have{d_key_index != nullptr, d_roll != nullptr, d_superseded_by != nullptr, d_found != nullptr, d_roster_groups != nullptr,
                                  d_roster_weights != nullptr, d_groups_out != nullptr, d_weights_out != nullptr, d_displaced != nullptr,
                                  d_displaced_count != nullptr}));
-  TRY_(roll_check_aligned((uintptr_t)d_roll | (uintptr_t)d_roster_weights | (uintptr_t)d_superseded_by | (uintptr_t)d_weights_out |
-                              (uintptr_t)d_displaced | (uintptr_t)d_displaced_count,
-                          (uintptr_t)d_key_index | (uintptr_t)d_status_in | (uintptr_t)d_status_out | (uintptr_t)d_roster_groups |
-                              (uintptr_t)d_groups_out | (uintptr_t)d_found | (uintptr_t)d_scratch));
+  TRY_(check_aligned(ROLL_ALIGNED,
+                     (uintptr_t)d_roll | (uintptr_t)d_roster_weights | (uintptr_t)d_superseded_by | (uintptr_t)d_weights_out |
+                         (uintptr_t)d_displaced | (uintptr_t)d_displaced_count,
+                     (uintptr_t)d_key_index | (uintptr_t)d_status_in | (uintptr_t)d_status_out | (uintptr_t)d_roster_groups |
+                         (uintptr_t)d_groups_out | (uintptr_t)d_found | (uintptr_t)d_scratch));
   const egr::Layout L = egr::layout(n, n_keys);
   if (L.total && (!d_scratch || scratch_bytes < L.total))
     return fail(EG_ERR_BAD_ARG, "roll: scratch is null or too small (eg_roll_cast_scratch_bytes says how much)");
-  TRY_(roll_check_ctx(c));
+  TRY_(check_ctx("roll", c));
   if (!d_found && !d_displaced_count) return EG_OK;                       // n == 0 and nowhere to write anything to
   HIPCHK(hipSetDevice(c->device));
   hipStream_t s = (hipStream_t)stream;
@@ -4280,10 +4243,10 @@ int eg_roll_check_device(eg_ctx* c, size_t n, const void* d_key_index, const voi
   TRY_(roll_check_args(n, n_keys, seq_base, policy,
                        egr::Have{d_key_index != nullptr, d_roll != nullptr, d_superseded_by != nullptr, d_found != nullptr, d_roster_groups != nullptr,
                                  d_roster_weights != nullptr, d_groups_out != nullptr, d_weights_out != nullptr, false, false}));
-  TRY_(roll_check_aligned((uintptr_t)d_roll | (uintptr_t)d_roster_weights | (uintptr_t)d_superseded_by | (uintptr_t)d_weights_out,
-                          (uintptr_t)d_key_index | (uintptr_t)d_status_in | (uintptr_t)d_status_out | (uintptr_t)d_roster_groups |
-                              (uintptr_t)d_groups_out | (uintptr_t)d_found));
-  TRY_(roll_check_ctx(c));
+  TRY_(check_aligned(ROLL_ALIGNED, (uintptr_t)d_roll | (uintptr_t)d_roster_weights | (uintptr_t)d_superseded_by | (uintptr_t)d_weights_out,
+                     (uintptr_t)d_key_index | (uintptr_t)d_status_in | (uintptr_t)d_status_out | (uintptr_t)d_roster_groups |
+                         (uintptr_t)d_groups_out | (uintptr_t)d_found));
+  TRY_(check_ctx("roll", c));
   if (!d_found) return EG_OK;                                             // n == 0 and nowhere to write anything to
   HIPCHK(hipSetDevice(c->device));
   hipStream_t s = (hipStream_t)stream;
@@ -4309,12 +4272,12 @@ static int roll_host(eg_ctx* c, bool cast, size_t n, const uint32_t* key_index, 
                        egr::Have{key_index != nullptr, roll != nullptr, superseded_by != nullptr, found != nullptr, roster_groups != nullptr,
                                  roster_weights != nullptr, groups_out != nullptr, weights_out != nullptr, displaced != nullptr,
                                  displaced_count != nullptr}));
-  TRY_(roll_check_ctx(c));
+  TRY_(check_ctx("roll", c));
   if (found) found[0] = found[1] = found[2] = 0;
   if (displaced_count) *displaced_count = 0;
   if (n == 0) return EG_OK;
   HIPCHK(hipSetDevice(c->device));
-  EdStage st; st.who = "roll"; TRY_(st.open());
+  HostStage st("roll"); TRY_(st.open());
   const size_t need = cast ? eg_roll_cast_scratch_bytes(c, n, n_keys) : 0;
   void *di, *dsi = nullptr, *dr, *dg = nullptr, *dw = nullptr, *dby, *dso = nullptr, *dgo = nullptr, *dwo = nullptr, *dd = nullptr, *dtail, *scratch = nullptr;
   TRY_(st.put(&di, key_index, n * 4));
@@ -4336,17 +4299,17 @@ static int roll_host(eg_ctx* c, bool cast, size_t n, const uint32_t* key_index, 
   else
     TRY_(eg_roll_check_device(c, n, di, dsi, seq_base, policy, dr, n_keys, dg, dw, dby, dso, dgo, dwo, d_found, st.s));
   unsigned long long count = 0;
-  HIPCHK(hipMemcpyAsync(superseded_by, dby, n * 8, hipMemcpyDeviceToHost, st.s));
-  if (status_out) HIPCHK(hipMemcpyAsync(status_out, dso, n * 4, hipMemcpyDeviceToHost, st.s));
-  if (groups_out) HIPCHK(hipMemcpyAsync(groups_out, dgo, n * 4, hipMemcpyDeviceToHost, st.s));
-  if (weights_out) HIPCHK(hipMemcpyAsync(weights_out, dwo, n * 8, hipMemcpyDeviceToHost, st.s));
-  if (cast) HIPCHK(hipMemcpyAsync(roll_out, dr, n_keys * 8, hipMemcpyDeviceToHost, st.s));
-  HIPCHK(hipMemcpyAsync(found, d_found, 3 * sizeof(u32), hipMemcpyDeviceToHost, st.s));
-  if (displaced) HIPCHK(hipMemcpyAsync(&count, d_count, sizeof count, hipMemcpyDeviceToHost, st.s));
-  HIPCHK(hipStreamSynchronize(st.s));
+  TRY_(st.get(superseded_by, dby, n * 8));
+  if (status_out) TRY_(st.get(status_out, dso, n * 4));
+  if (groups_out) TRY_(st.get(groups_out, dgo, n * 4));
+  if (weights_out) TRY_(st.get(weights_out, dwo, n * 8));
+  if (cast) TRY_(st.get(roll_out, dr, n_keys * 8));
+  TRY_(st.get(found, d_found, 3 * sizeof(u32)));
+  if (displaced) TRY_(st.get(&count, d_count, sizeof count));
+  TRY_(st.sync());
   if (displaced && count && count <= n) {
-    HIPCHK(hipMemcpyAsync(displaced, dd, (size_t)count * 16, hipMemcpyDeviceToHost, st.s));
-    HIPCHK(hipStreamSynchronize(st.s));
+    TRY_(st.get(displaced, dd, (size_t)count * 16));
+    TRY_(st.sync());
   }
   if (displaced_count) *displaced_count = count;
   return EG_OK;
@@ -4369,12 +4332,8 @@ int eg_roll_check(eg_ctx* c, size_t n, const uint32_t* key_index, const uint32_t
 // in the _device forms.  The argument rules come first and need no context (so they can be tested without a GPU); what passes them fails on
 // a null context.
 static int merkle_refuse(const char* why) { return why ? fail(EG_ERR_BAD_ARG, std::string("merkle: ") + why) : EG_OK; }
-static int merkle_check_ctx(const eg_ctx* c) { return c ? EG_OK : fail(EG_ERR_BAD_ARG, "merkle: null ctx"); }
-static int merkle_check_aligned(uintptr_t words64, uintptr_t words32) {
-  if (words64 & 7u) return fail(EG_ERR_BAD_ARG, "merkle: leaf_index, log_count and index must be 8-byte aligned");
-  if (words32 & 3u) return fail(EG_ERR_BAD_ARG, "merkle: leaves, log, nodes, paths, root, path_len, verdict, the status words, found and scratch must be 4-byte aligned");
-  return EG_OK;
-}
+static const AlignedMsgs MERKLE_ALIGNED{"merkle: leaf_index, log_count and index must be 8-byte aligned",
+                                        "merkle: leaves, log, nodes, paths, root, path_len, verdict, the status words, found and scratch must be 4-byte aligned"};
 int eg_merkle_depth(uint64_t n_leaves) { return egm::depth(n_leaves); }
 size_t eg_merkle_nodes_bytes(uint64_t n_leaves) { return n_leaves < egm::LEAVES_MAX ? (size_t)egm::nodes_total(n_leaves) * egm::HASH_BYTES : 0; }
 int eg_merkle_level(uint64_t n_leaves, int level, uint64_t* offset, uint64_t* count) {
@@ -4429,11 +4388,11 @@ int eg_merkle_leaves_device(eg_ctx* c, size_t n, const void* d_msgs, size_t msg_
   TRY_(merkle_refuse(egm::refuse_messages(n, d_msgs != nullptr, msg_stride, msg_len, prefix != nullptr, prefix_len, d_extra != nullptr, extra_stride,
                                           extra_len)));
   TRY_(merkle_refuse(egm::refuse_leaves(n, n_prior, d_leaf_index != nullptr, d_found != nullptr, d_log != nullptr, d_log_count != nullptr, log_cap)));
-  TRY_(merkle_check_aligned((uintptr_t)d_leaf_index | (uintptr_t)d_log_count,
-                            (uintptr_t)d_leaves_out | (uintptr_t)d_log | (uintptr_t)d_status_in | (uintptr_t)d_found | (uintptr_t)d_scratch));
+  TRY_(check_aligned(MERKLE_ALIGNED, (uintptr_t)d_leaf_index | (uintptr_t)d_log_count,
+                     (uintptr_t)d_leaves_out | (uintptr_t)d_log | (uintptr_t)d_status_in | (uintptr_t)d_found | (uintptr_t)d_scratch));
   const size_t need = egm::leaf_layout(n).total;
   if (need && (!d_scratch || scratch_bytes < need)) return merkle_refuse("scratch is null or too small (eg_merkle_leaves_scratch_bytes says how much)");
-  TRY_(merkle_check_ctx(c));
+  TRY_(check_ctx("merkle", c));
   const MerkleItems it{static_cast<const unsigned char*>(d_msgs), msg_stride, msg_len, extra_len ? static_cast<const unsigned char*>(d_extra) : nullptr,
                        extra_stride, extra_len, nullptr, 0};
   u32* tail = d_log_count ? static_cast<u32*>(d_log) + n_prior * egm::HASH_WORDS : nullptr;
@@ -4445,12 +4404,12 @@ int eg_merkle_leaves(eg_ctx* c, size_t n, const uint8_t* msgs, size_t msg_stride
                      uint8_t* leaves_out, uint8_t* log, uint64_t log_cap, uint64_t* log_count, uint32_t* found) {
   TRY_(merkle_refuse(egm::refuse_messages(n, msgs != nullptr, msg_stride, msg_len, prefix != nullptr, prefix_len, extra != nullptr, extra_stride, extra_len)));
   TRY_(merkle_refuse(egm::refuse_leaves(n, n_prior, leaf_index != nullptr, found != nullptr, log != nullptr, log_count != nullptr, log_cap)));
-  TRY_(merkle_check_ctx(c));
+  TRY_(check_ctx("merkle", c));
   if (found) found[0] = found[1] = 0;
   if (log_count) *log_count = n_prior;
   if (n == 0) return EG_OK;
   HIPCHK(hipSetDevice(c->device));
-  EdStage st; st.who = "merkle"; TRY_(st.open());
+  HostStage st("merkle"); TRY_(st.open());
   const size_t need = eg_merkle_leaves_scratch_bytes(n);
   const uint64_t room = log_count ? log_cap - n_prior : 0u;
   const size_t tail_rows = (size_t)std::min<uint64_t>(room, n);       // at most n leaves are appended, and never more than fit
@@ -4469,14 +4428,14 @@ int eg_merkle_leaves(eg_ctx* c, size_t n, const uint8_t* msgs, size_t msg_stride
   TRY_(merkle_leaves_run(c, n, it, prefix, prefix_len, static_cast<const u32*>(dsi), n_prior, di, dl, static_cast<u32*>(dt), room, d_count, d_found,
                          scratch, st.s));
   unsigned long long count = n_prior;
-  HIPCHK(hipMemcpyAsync(leaf_index, di, n * 8, hipMemcpyDeviceToHost, st.s));
-  if (leaves_out) HIPCHK(hipMemcpyAsync(leaves_out, dl, n * egm::HASH_BYTES, hipMemcpyDeviceToHost, st.s));
-  HIPCHK(hipMemcpyAsync(found, d_found, 2 * sizeof(u32), hipMemcpyDeviceToHost, st.s));
-  if (log_count) HIPCHK(hipMemcpyAsync(&count, d_count, sizeof count, hipMemcpyDeviceToHost, st.s));
-  HIPCHK(hipStreamSynchronize(st.s));
+  TRY_(st.get(leaf_index, di, n * 8));
+  if (leaves_out) TRY_(st.get(leaves_out, dl, n * egm::HASH_BYTES));
+  TRY_(st.get(found, d_found, 2 * sizeof(u32)));
+  if (log_count) TRY_(st.get(&count, d_count, sizeof count));
+  TRY_(st.sync());
   if (log_count && count > n_prior && count - n_prior <= tail_rows) {
-    HIPCHK(hipMemcpyAsync(log + n_prior * egm::HASH_BYTES, dt, (size_t)(count - n_prior) * egm::HASH_BYTES, hipMemcpyDeviceToHost, st.s));
-    HIPCHK(hipStreamSynchronize(st.s));
+    TRY_(st.get(log + n_prior * egm::HASH_BYTES, dt, (size_t)(count - n_prior) * egm::HASH_BYTES));
+    TRY_(st.sync());
   }
   if (log_count) *log_count = count;
   if (found[1]) return fail(EG_ERR_BAD_ARG, "merkle: the leaves do not fit the log (log_cap); nothing was appended");
@@ -4486,11 +4445,11 @@ int eg_merkle_leaves(eg_ctx* c, size_t n, const uint8_t* msgs, size_t msg_stride
 int eg_merkle_tree_device(eg_ctx* c, uint64_t n_leaves, const void* d_log, void* d_root, void* d_nodes, void* d_scratch, size_t scratch_bytes,
                           void* stream) {
   TRY_(merkle_refuse(egm::refuse_tree(n_leaves, d_log != nullptr, d_root != nullptr)));
-  TRY_(merkle_check_aligned(0, (uintptr_t)d_log | (uintptr_t)d_root | (uintptr_t)d_nodes | (uintptr_t)d_scratch));
+  TRY_(check_aligned(MERKLE_ALIGNED, 0, (uintptr_t)d_log | (uintptr_t)d_root | (uintptr_t)d_nodes | (uintptr_t)d_scratch));
   const egm::TreeLayout L = egm::tree_layout(n_leaves);
   if (!d_nodes && L.total && (!d_scratch || scratch_bytes < L.total))
     return merkle_refuse("scratch is null or too small (eg_merkle_tree_scratch_bytes says how much a tree without a node store needs)");
-  TRY_(merkle_check_ctx(c));
+  TRY_(check_ctx("merkle", c));
   HIPCHK(hipSetDevice(c->device));
   hipStream_t s = (hipStream_t)stream;
   const u32* cur = static_cast<const u32*>(d_log);
@@ -4519,9 +4478,9 @@ int eg_merkle_tree_device(eg_ctx* c, uint64_t n_leaves, const void* d_log, void*
 }
 int eg_merkle_tree(eg_ctx* c, uint64_t n_leaves, const uint8_t* log, uint8_t* root, uint8_t* nodes) {
   TRY_(merkle_refuse(egm::refuse_tree(n_leaves, log != nullptr, root != nullptr)));
-  TRY_(merkle_check_ctx(c));
+  TRY_(check_ctx("merkle", c));
   HIPCHK(hipSetDevice(c->device));
-  EdStage st; st.who = "merkle"; TRY_(st.open());
+  HostStage st("merkle"); TRY_(st.open());
   const size_t store_bytes = eg_merkle_nodes_bytes(n_leaves), need = nodes ? 0 : eg_merkle_tree_scratch_bytes(n_leaves);
   void *dl = nullptr, *dr, *dn = nullptr, *scratch = nullptr;
   if (n_leaves) TRY_(st.put(&dl, log, (size_t)n_leaves * egm::HASH_BYTES));
@@ -4529,17 +4488,17 @@ int eg_merkle_tree(eg_ctx* c, uint64_t n_leaves, const uint8_t* log, uint8_t* ro
   if (nodes) TRY_(st.put(&dn, nullptr, store_bytes));
   if (need) TRY_(st.put(&scratch, nullptr, need));
   TRY_(eg_merkle_tree_device(c, n_leaves, dl, dr, dn, scratch, need, st.s));
-  HIPCHK(hipMemcpyAsync(root, dr, egm::HASH_BYTES, hipMemcpyDeviceToHost, st.s));
-  if (nodes && store_bytes) HIPCHK(hipMemcpyAsync(nodes, dn, store_bytes, hipMemcpyDeviceToHost, st.s));
-  HIPCHK(hipStreamSynchronize(st.s));
+  TRY_(st.get(root, dr, egm::HASH_BYTES));
+  if (nodes && store_bytes) TRY_(st.get(nodes, dn, store_bytes));
+  TRY_(st.sync());
   return EG_OK;
 }
 
 int eg_merkle_paths_device(eg_ctx* c, size_t m, const void* d_index, uint64_t n_leaves, const void* d_log, const void* d_nodes, void* d_paths,
                            void* d_path_len, void* stream) {
   TRY_(merkle_refuse(egm::refuse_paths(m, n_leaves, d_index != nullptr, d_log != nullptr, d_nodes != nullptr, d_paths != nullptr, d_path_len != nullptr)));
-  TRY_(merkle_check_aligned((uintptr_t)d_index, (uintptr_t)d_log | (uintptr_t)d_nodes | (uintptr_t)d_paths | (uintptr_t)d_path_len));
-  TRY_(merkle_check_ctx(c));
+  TRY_(check_aligned(MERKLE_ALIGNED, (uintptr_t)d_index, (uintptr_t)d_log | (uintptr_t)d_nodes | (uintptr_t)d_paths | (uintptr_t)d_path_len));
+  TRY_(check_ctx("merkle", c));
   if (m == 0) return EG_OK;
   HIPCHK(hipSetDevice(c->device));
   const int depth = egm::depth(n_leaves);
@@ -4552,10 +4511,10 @@ int eg_merkle_paths_device(eg_ctx* c, size_t m, const void* d_index, uint64_t n_
 int eg_merkle_paths(eg_ctx* c, size_t m, const uint64_t* index, uint64_t n_leaves, const uint8_t* log, const uint8_t* nodes, uint8_t* paths,
                     uint32_t* path_len) {
   TRY_(merkle_refuse(egm::refuse_paths(m, n_leaves, index != nullptr, log != nullptr, nodes != nullptr, paths != nullptr, path_len != nullptr)));
-  TRY_(merkle_check_ctx(c));
+  TRY_(check_ctx("merkle", c));
   if (m == 0) return EG_OK;
   HIPCHK(hipSetDevice(c->device));
-  EdStage st; st.who = "merkle"; TRY_(st.open());
+  HostStage st("merkle"); TRY_(st.open());
   const size_t row = egm::HASH_BYTES * (size_t)egm::depth(n_leaves);
   void *di, *dl = nullptr, *dn = nullptr, *dp = nullptr, *dlen;
   TRY_(st.put(&di, index, m * 8));
@@ -4566,9 +4525,9 @@ int eg_merkle_paths(eg_ctx* c, size_t m, const uint64_t* index, uint64_t n_leave
   }
   TRY_(st.put(&dlen, nullptr, m * 4));
   TRY_(eg_merkle_paths_device(c, m, di, n_leaves, dl, dn, dp, dlen, st.s));
-  if (row) HIPCHK(hipMemcpyAsync(paths, dp, m * row, hipMemcpyDeviceToHost, st.s));
-  HIPCHK(hipMemcpyAsync(path_len, dlen, m * 4, hipMemcpyDeviceToHost, st.s));
-  HIPCHK(hipStreamSynchronize(st.s));
+  if (row) TRY_(st.get(paths, dp, m * row));
+  TRY_(st.get(path_len, dlen, m * 4));
+  TRY_(st.sync());
   return EG_OK;
 }
 
@@ -4576,9 +4535,9 @@ int eg_merkle_check_device(eg_ctx* c, size_t m, const void* d_index, const void*
                            const void* d_path_len, uint64_t n_leaves, const void* d_root, void* d_verdict, void* d_found, void* stream) {
   TRY_(merkle_refuse(egm::refuse_check(m, n_leaves, d_index != nullptr, d_leaves != nullptr, d_paths != nullptr, path_stride, d_path_len != nullptr,
                                        d_root != nullptr, d_verdict != nullptr, d_found != nullptr)));
-  TRY_(merkle_check_aligned((uintptr_t)d_index, (uintptr_t)d_leaves | (uintptr_t)d_paths | (uintptr_t)d_path_len | (uintptr_t)d_root |
-                                                    (uintptr_t)d_verdict | (uintptr_t)d_found));
-  TRY_(merkle_check_ctx(c));
+  TRY_(check_aligned(MERKLE_ALIGNED, (uintptr_t)d_index, (uintptr_t)d_leaves | (uintptr_t)d_paths | (uintptr_t)d_path_len | (uintptr_t)d_root |
+                                                         (uintptr_t)d_verdict | (uintptr_t)d_found));
+  TRY_(check_ctx("merkle", c));
   if (!d_found) return EG_OK;                                           // m == 0 and nowhere to write anything to
   HIPCHK(hipSetDevice(c->device));
   hipStream_t s = (hipStream_t)stream;
@@ -4596,11 +4555,11 @@ int eg_merkle_check(eg_ctx* c, size_t m, const uint64_t* index, const uint8_t* l
                     const uint32_t* path_len, uint64_t n_leaves, const uint8_t* root, uint32_t* verdict, uint32_t* found) {
   TRY_(merkle_refuse(egm::refuse_check(m, n_leaves, index != nullptr, leaves != nullptr, paths != nullptr, path_stride, path_len != nullptr,
                                        root != nullptr, verdict != nullptr, found != nullptr)));
-  TRY_(merkle_check_ctx(c));
+  TRY_(check_ctx("merkle", c));
   if (found) found[0] = found[1] = found[2] = 0;
   if (m == 0) return EG_OK;
   HIPCHK(hipSetDevice(c->device));
-  EdStage st; st.who = "merkle"; TRY_(st.open());
+  HostStage st("merkle"); TRY_(st.open());
   void *di, *dl, *dp = nullptr, *dlen, *dr, *dv, *df;
   TRY_(st.put(&di, index, m * 8));
   TRY_(st.put(&dl, leaves, m * egm::HASH_BYTES));
@@ -4610,25 +4569,22 @@ int eg_merkle_check(eg_ctx* c, size_t m, const uint64_t* index, const uint8_t* l
   TRY_(st.put(&dv, nullptr, m * 4));
   TRY_(st.put(&df, nullptr, 16));
   TRY_(eg_merkle_check_device(c, m, di, dl, dp, path_stride, dlen, n_leaves, dr, dv, df, st.s));
-  HIPCHK(hipMemcpyAsync(verdict, dv, m * 4, hipMemcpyDeviceToHost, st.s));
-  HIPCHK(hipMemcpyAsync(found, df, 3 * sizeof(u32), hipMemcpyDeviceToHost, st.s));
-  HIPCHK(hipStreamSynchronize(st.s));
+  TRY_(st.get(verdict, dv, m * 4));
+  TRY_(st.get(found, df, 3 * sizeof(u32)));
+  TRY_(st.sync());
   return EG_OK;
 }
 
 // ---- receipt log, the audit entries: past heads, consistency proofs and their check (merkle_audit_kernels.cuh), out of the node store ----
-static int merkle_audit_aligned(uintptr_t words64, uintptr_t words32) {
-  if (words64 & 7u) return fail(EG_ERR_BAD_ARG, "merkle: size and old_size must be 8-byte aligned");
-  if (words32 & 3u) return fail(EG_ERR_BAD_ARG, "merkle: log, nodes, heads, proofs, old_root, root, proof_len, verdict and found must be 4-byte aligned");
-  return EG_OK;
-}
+static const AlignedMsgs MERKLE_AUDIT_ALIGNED{"merkle: size and old_size must be 8-byte aligned",
+                                              "merkle: log, nodes, heads, proofs, old_root, root, proof_len, verdict and found must be 4-byte aligned"};
 uint32_t eg_merkle_consistency_len(uint64_t old_size, uint64_t n_leaves) { return egm::consistency_len(old_size, n_leaves); }
 
 int eg_merkle_heads_device(eg_ctx* c, size_t m, const void* d_size, uint64_t n_leaves, const void* d_log, const void* d_nodes, void* d_heads,
                            void* d_found, void* stream) {
   TRY_(merkle_refuse(egm::refuse_heads(m, n_leaves, d_size != nullptr, d_log != nullptr, d_nodes != nullptr, d_heads != nullptr, d_found != nullptr)));
-  TRY_(merkle_audit_aligned((uintptr_t)d_size, (uintptr_t)d_log | (uintptr_t)d_nodes | (uintptr_t)d_heads | (uintptr_t)d_found));
-  TRY_(merkle_check_ctx(c));
+  TRY_(check_aligned(MERKLE_AUDIT_ALIGNED, (uintptr_t)d_size, (uintptr_t)d_log | (uintptr_t)d_nodes | (uintptr_t)d_heads | (uintptr_t)d_found));
+  TRY_(check_ctx("merkle", c));
   if (!d_found) return EG_OK;                                           // m == 0 and nowhere to write anything to
   HIPCHK(hipSetDevice(c->device));
   hipStream_t s = (hipStream_t)stream;
@@ -4644,11 +4600,11 @@ int eg_merkle_heads_device(eg_ctx* c, size_t m, const void* d_size, uint64_t n_l
 int eg_merkle_heads(eg_ctx* c, size_t m, const uint64_t* size, uint64_t n_leaves, const uint8_t* log, const uint8_t* nodes, uint8_t* heads,
                     uint32_t* found) {
   TRY_(merkle_refuse(egm::refuse_heads(m, n_leaves, size != nullptr, log != nullptr, nodes != nullptr, heads != nullptr, found != nullptr)));
-  TRY_(merkle_check_ctx(c));
+  TRY_(check_ctx("merkle", c));
   if (found) found[0] = 0;
   if (m == 0) return EG_OK;
   HIPCHK(hipSetDevice(c->device));
-  EdStage st; st.who = "merkle"; TRY_(st.open());
+  HostStage st("merkle"); TRY_(st.open());
   void *ds, *dl = nullptr, *dn = nullptr, *dh, *df;
   TRY_(st.put(&ds, size, m * 8));
   if (n_leaves > 0) TRY_(st.put(&dl, log, (size_t)n_leaves * egm::HASH_BYTES));
@@ -4656,9 +4612,9 @@ int eg_merkle_heads(eg_ctx* c, size_t m, const uint64_t* size, uint64_t n_leaves
   TRY_(st.put(&dh, nullptr, m * egm::HASH_BYTES));
   TRY_(st.put(&df, nullptr, 16));
   TRY_(eg_merkle_heads_device(c, m, ds, n_leaves, dl, dn, dh, df, st.s));
-  HIPCHK(hipMemcpyAsync(heads, dh, m * egm::HASH_BYTES, hipMemcpyDeviceToHost, st.s));
-  HIPCHK(hipMemcpyAsync(found, df, sizeof(u32), hipMemcpyDeviceToHost, st.s));
-  HIPCHK(hipStreamSynchronize(st.s));
+  TRY_(st.get(heads, dh, m * egm::HASH_BYTES));
+  TRY_(st.get(found, df, sizeof(u32)));
+  TRY_(st.sync());
   return EG_OK;
 }
 
@@ -4666,8 +4622,8 @@ int eg_merkle_consistency_device(eg_ctx* c, size_t m, const void* d_old_size, ui
                                  void* d_proofs, void* d_proof_len, void* stream) {
   TRY_(merkle_refuse(egm::refuse_consistency(m, n_leaves, d_old_size != nullptr, d_log != nullptr, d_nodes != nullptr, d_proofs != nullptr,
                                              d_proof_len != nullptr)));
-  TRY_(merkle_audit_aligned((uintptr_t)d_old_size, (uintptr_t)d_log | (uintptr_t)d_nodes | (uintptr_t)d_proofs | (uintptr_t)d_proof_len));
-  TRY_(merkle_check_ctx(c));
+  TRY_(check_aligned(MERKLE_AUDIT_ALIGNED, (uintptr_t)d_old_size, (uintptr_t)d_log | (uintptr_t)d_nodes | (uintptr_t)d_proofs | (uintptr_t)d_proof_len));
+  TRY_(check_ctx("merkle", c));
   if (m == 0) return EG_OK;
   HIPCHK(hipSetDevice(c->device));
   const int row = (int)egm::consistency_row(n_leaves);
@@ -4680,10 +4636,10 @@ int eg_merkle_consistency_device(eg_ctx* c, size_t m, const void* d_old_size, ui
 int eg_merkle_consistency(eg_ctx* c, size_t m, const uint64_t* old_size, uint64_t n_leaves, const uint8_t* log, const uint8_t* nodes, uint8_t* proofs,
                           uint32_t* proof_len) {
   TRY_(merkle_refuse(egm::refuse_consistency(m, n_leaves, old_size != nullptr, log != nullptr, nodes != nullptr, proofs != nullptr, proof_len != nullptr)));
-  TRY_(merkle_check_ctx(c));
+  TRY_(check_ctx("merkle", c));
   if (m == 0) return EG_OK;
   HIPCHK(hipSetDevice(c->device));
-  EdStage st; st.who = "merkle"; TRY_(st.open());
+  HostStage st("merkle"); TRY_(st.open());
   const size_t row = egm::HASH_BYTES * egm::consistency_row(n_leaves);
   void *ds, *dl = nullptr, *dn = nullptr, *dp, *dlen;
   TRY_(st.put(&ds, old_size, m * 8));
@@ -4692,9 +4648,9 @@ int eg_merkle_consistency(eg_ctx* c, size_t m, const uint64_t* old_size, uint64_
   TRY_(st.put(&dp, nullptr, m * row));
   TRY_(st.put(&dlen, nullptr, m * 4));
   TRY_(eg_merkle_consistency_device(c, m, ds, n_leaves, dl, dn, dp, dlen, st.s));
-  HIPCHK(hipMemcpyAsync(proofs, dp, m * row, hipMemcpyDeviceToHost, st.s));
-  HIPCHK(hipMemcpyAsync(proof_len, dlen, m * 4, hipMemcpyDeviceToHost, st.s));
-  HIPCHK(hipStreamSynchronize(st.s));
+  TRY_(st.get(proofs, dp, m * row));
+  TRY_(st.get(proof_len, dlen, m * 4));
+  TRY_(st.sync());
   return EG_OK;
 }
 
@@ -4702,9 +4658,9 @@ int eg_merkle_consistency_check_device(eg_ctx* c, size_t m, const void* d_old_si
                                        const void* d_proof_len, uint64_t n_leaves, const void* d_root, void* d_verdict, void* d_found, void* stream) {
   TRY_(merkle_refuse(egm::refuse_consistency_check(m, n_leaves, d_old_size != nullptr, d_old_root != nullptr, d_proofs != nullptr, proof_stride,
                                                    d_proof_len != nullptr, d_root != nullptr, d_verdict != nullptr, d_found != nullptr)));
-  TRY_(merkle_audit_aligned((uintptr_t)d_old_size, (uintptr_t)d_old_root | (uintptr_t)d_proofs | (uintptr_t)d_proof_len | (uintptr_t)d_root |
-                                                       (uintptr_t)d_verdict | (uintptr_t)d_found));
-  TRY_(merkle_check_ctx(c));
+  TRY_(check_aligned(MERKLE_AUDIT_ALIGNED, (uintptr_t)d_old_size, (uintptr_t)d_old_root | (uintptr_t)d_proofs | (uintptr_t)d_proof_len | (uintptr_t)d_root |
+                                                                  (uintptr_t)d_verdict | (uintptr_t)d_found));
+  TRY_(check_ctx("merkle", c));
   if (!d_found) return EG_OK;                                           // m == 0 and nowhere to write anything to
   HIPCHK(hipSetDevice(c->device));
   hipStream_t s = (hipStream_t)stream;
@@ -4723,11 +4679,11 @@ int eg_merkle_consistency_check(eg_ctx* c, size_t m, const uint64_t* old_size, c
                                 const uint32_t* proof_len, uint64_t n_leaves, const uint8_t* root, uint32_t* verdict, uint32_t* found) {
   TRY_(merkle_refuse(egm::refuse_consistency_check(m, n_leaves, old_size != nullptr, old_root != nullptr, proofs != nullptr, proof_stride,
                                                    proof_len != nullptr, root != nullptr, verdict != nullptr, found != nullptr)));
-  TRY_(merkle_check_ctx(c));
+  TRY_(check_ctx("merkle", c));
   if (found) found[0] = found[1] = found[2] = found[3] = 0;
   if (m == 0) return EG_OK;
   HIPCHK(hipSetDevice(c->device));
-  EdStage st; st.who = "merkle"; TRY_(st.open());
+  HostStage st("merkle"); TRY_(st.open());
   void *ds, *dor, *dp = nullptr, *dlen, *dr, *dv, *df;
   TRY_(st.put(&ds, old_size, m * 8));
   TRY_(st.put(&dor, old_root, m * egm::HASH_BYTES));
@@ -4737,9 +4693,9 @@ int eg_merkle_consistency_check(eg_ctx* c, size_t m, const uint64_t* old_size, c
   TRY_(st.put(&dv, nullptr, m * 4));
   TRY_(st.put(&df, nullptr, 16));
   TRY_(eg_merkle_consistency_check_device(c, m, ds, dor, dp, proof_stride, dlen, n_leaves, dr, dv, df, st.s));
-  HIPCHK(hipMemcpyAsync(verdict, dv, m * 4, hipMemcpyDeviceToHost, st.s));
-  HIPCHK(hipMemcpyAsync(found, df, 4 * sizeof(u32), hipMemcpyDeviceToHost, st.s));
-  HIPCHK(hipStreamSynchronize(st.s));
+  TRY_(st.get(verdict, dv, m * 4));
+  TRY_(st.get(found, df, 4 * sizeof(u32)));
+  TRY_(st.sync());
   return EG_OK;
 }
 

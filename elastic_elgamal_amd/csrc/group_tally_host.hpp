@@ -15,6 +15,7 @@
 #include <stdint.h>
 #include <vector>
 #include "plan.h"
+#include "scan_host.hpp"
 
 #if defined(__HIPCC__)
 #define EGGT_HD __host__ __device__ inline
@@ -31,7 +32,6 @@ constexpr uint32_t GROUPS_MAX = 1u << 24;         // EG_TALLY_GROUPS_MAX
 constexpr uint64_t N_LIMIT = 1ull << 31;          // n must stay below: ballot indices and list offsets are 32-bit
 constexpr int MAX_LEVELS = 7;                     // ceil(2^31 / 32) = 2^26 pieces -> 2^21 -> 2^16 -> 2^11 -> 2^6 -> 2 -> 1
 constexpr int SEQ = MAX_LEVELS + 1;               // sequences of the scan: list offsets + pieces of every level
-constexpr uint32_t SCAN_TILE = 1024;              // groups per block of the scan kernels
 constexpr size_t POINT_BYTES = 144;               // a partial sum: 36 limbs (device_io.cuh: PT_WORDS)
 
 EGGT_HD uint32_t ceil_div(uint32_t a, uint32_t b) { return a / b + (a % b ? 1u : 0u); }
@@ -87,7 +87,7 @@ struct Layout {
 inline Layout layout(size_t n, uint32_t n_groups, uint32_t n_slots, uint32_t s1 = S1, uint32_t s2 = S2) {
   Layout L;
   L.n_levels = levels(n, s1, s2);
-  L.n_tiles = (n_groups + SCAN_TILE - 1) / SCAN_TILE;
+  L.n_tiles = egscan::scan_tiles(n_groups);
   size_t off = 0;
   auto take = [&](size_t bytes) { const size_t at = off; off += (bytes + 255) / 256 * 256; return at; };
   const size_t g = (size_t)n_groups * sizeof(uint32_t);

@@ -9,8 +9,8 @@
 //   k_gt_count       one lane = one ballot: accepted and id in range -> count[id] += 1 (wave-aggregated: one precinct may hold half of all
 //                    ballots); an accepted ballot with an id >= n_groups other than EG_GROUP_NONE counts in bad[0].  Ids of rejected
 //                    ballots are never read.
-//   k_gt_scan_*      prefix sums over the groups (tiles of 1024, as k_pip_scan_*; those kernels have the piece sizes of the bucket
-//                    method built in, so they are not shared): list offsets, and pieces / first piece per group for every level at once
+//   k_gt_scan_*      prefix sums over the groups (the three bodies of scan.cuh, which k_pip_scan_* wrap too, around this pass's piece
+//                    sizes): list offsets, and pieces / first piece per group for every level at once
 //   k_gt_fill        one lane = one ballot: append its index to its group's list (atomic cursor: the ORDER inside a list depends on
 //                    timing, the sum does not - and the result is a canonical encoding)
 //   k_gt_sum_wire    one lane = one piece x one tally slot: load the slot's wire item of up to S1 ballots (two 128-bit loads), decode, add.
@@ -229,72 +229,25 @@ __global__ void __launch_bounds__(NT) k_gt_fill(u32 n, const u32* status, const 
   if (in && at < n) idx[at] = b;                                   // ... unless the caller let the status words change in between
 }
 
-// ---- prefix sums over the groups, for the lists and for every level of pieces at once (three launches, as k_pip_scan_*) ----------------
+// ---- prefix sums over the groups, for the lists and for every level of pieces at once (three launches: scan.cuh) ----------------------
+struct GtLoad {
+  const u32* counts; u32 n; int levels; u32 s1, s2;
+  __device__ __forceinline__ void operator()(u32 v[GT_SEQ], u32 i) const { eggt::pieces_tuple(v, i < n ? counts[i] : 0u, levels, s1, s2); }
+};
 __global__ void __launch_bounds__(NT) k_gt_scan_tiles(const u32* counts, u32 n, int levels, u32 s1, u32 s2, GtScan S) {
-  __shared__ u32 red[GT_SEQ][NT / 64];
-  u32 sum[GT_SEQ];
-#pragma unroll
-  for (int k = 0; k < GT_SEQ; ++k) sum[k] = 0u;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const u32 i = blockIdx.x * eggt::SCAN_TILE + threadIdx.x * 4u + e;
-    u32 v[GT_SEQ];
-    eggt::pieces_tuple(v, i < n ? counts[i] : 0u, levels, s1, s2);
-#pragma unroll
-    for (int k = 0; k < GT_SEQ; ++k) sum[k] += v[k];
-  }
-#pragma unroll
-  for (int k = 0; k < GT_SEQ; ++k) {
-    u32 x = sum[k];
-    for (int off = 32; off >= 1; off >>= 1) x += (u32)__shfl_down((int)x, off, 64);
-    if ((threadIdx.x & 63) == 0) red[k][threadIdx.x >> 6] = x;
-  }
-  __syncthreads();
-  if (threadIdx.x < GT_SEQ) S.tile_sums[blockIdx.x * GT_SEQ + threadIdx.x] = red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3];
+  scan_tile_sums<GT_SEQ>(S.tile_sums, GtLoad{counts, n, levels, s1, s2});
 }
-__global__ void k_gt_scan_tops(u32 n_tiles, GtScan S) {            // one wavefront per sequence: tile sums -> exclusive prefix sums, totals
-  const int k = threadIdx.x >> 6, lane = threadIdx.x & 63;           // launched with 64 * GT_SEQ threads
-  u32 run = 0;
-  for (u32 b0 = 0; b0 < n_tiles; b0 += 64) {
-    const u32 b = b0 + lane;
-    const u32 v = b < n_tiles ? S.tile_sums[b * GT_SEQ + k] : 0u;
-    u32 x = v;
-    for (int off = 1; off < 64; off <<= 1) { const u32 y = (u32)__shfl_up((int)x, off, 64); if (lane >= off) x += y; }
-    if (b < n_tiles) S.tile_sums[b * GT_SEQ + k] = run + x - v;
-    run += (u32)__shfl((int)x, 63, 64);
-  }
-  if (lane == 0 && k >= 1) S.totals[k - 1] = run;
+__global__ void k_gt_scan_tops(u32 n_tiles, GtScan S) {            // launched with 64 * GT_SEQ threads
+  const u32 total = scan_tops<GT_SEQ>(n_tiles, S.tile_sums);
+  const int k = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0 && k >= 1) S.totals[k - 1] = total;
 }
 __global__ void __launch_bounds__(NT) k_gt_scan_apply(const u32* counts, u32 n, int levels, u32 s1, u32 s2, GtScan S) {
-  __shared__ u32 part[GT_SEQ][NT];
-  u32 v[4][GT_SEQ], sum[GT_SEQ];
+  u32 v[SCAN_PER_LANE][GT_SEQ], run[GT_SEQ];
+  scan_apply<GT_SEQ>(S.tile_sums, GtLoad{counts, n, levels, s1, s2}, v, run);
 #pragma unroll
-  for (int k = 0; k < GT_SEQ; ++k) sum[k] = 0u;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const u32 i = blockIdx.x * eggt::SCAN_TILE + threadIdx.x * 4u + e;
-    eggt::pieces_tuple(v[e], i < n ? counts[i] : 0u, levels, s1, s2);
-#pragma unroll
-    for (int k = 0; k < GT_SEQ; ++k) sum[k] += v[e][k];
-  }
-#pragma unroll
-  for (int k = 0; k < GT_SEQ; ++k) part[k][threadIdx.x] = sum[k];
-  __syncthreads();
-  for (int d = 1; d < NT; d <<= 1) {              // Hillis-Steele inclusive scan over the 256 lanes, all sequences together
-    u32 add[GT_SEQ];
-#pragma unroll
-    for (int k = 0; k < GT_SEQ; ++k) add[k] = (int)threadIdx.x >= d ? part[k][threadIdx.x - d] : 0u;
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < GT_SEQ; ++k) part[k][threadIdx.x] += add[k];
-    __syncthreads();
-  }
-  u32 run[GT_SEQ];
-#pragma unroll
-  for (int k = 0; k < GT_SEQ; ++k) run[k] = S.tile_sums[blockIdx.x * GT_SEQ + k] + (threadIdx.x ? part[k][threadIdx.x - 1] : 0u);
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const u32 i = blockIdx.x * eggt::SCAN_TILE + threadIdx.x * 4u + e;
+  for (int e = 0; e < SCAN_PER_LANE; ++e) {
+    const u32 i = scan_element(e);
     if (i < n) {
       S.offsets[i] = run[0];
 #pragma unroll

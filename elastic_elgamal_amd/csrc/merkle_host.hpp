@@ -9,6 +9,7 @@
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+#include "scan_host.hpp"
 
 #if defined(__HIPCC__)
 #define EGM_HD __host__ __device__ inline
@@ -27,7 +28,6 @@ constexpr uint64_t LEAVES_MAX = 1ull << 31;       // EG_MERKLE_LEAVES_MAX: n, m 
 constexpr size_t HASH_BYTES = 32;                 // EG_MERKLE_HASH_BYTES
 constexpr size_t HASH_WORDS = 8;
 constexpr size_t PREFIX_MAX = 255;
-constexpr uint32_t SCAN_TILE = 1024;              // ballots per block of the scan kernels
 constexpr int T_LOG = 10;                         // levels per launch of the tree: a tile of 2^T_LOG nodes per workgroup
 constexpr int MAX_DEPTH = 31;
 
@@ -111,7 +111,7 @@ inline LeafLayout leaf_layout(size_t n) {
   LeafLayout L;
   size_t off = 0;
   auto take = [&](size_t bytes) { const size_t at = off; off += (bytes + 255) / 256 * 256; return at; };
-  L.n_tiles = (uint32_t)((n + SCAN_TILE - 1) / SCAN_TILE);
+  L.n_tiles = egscan::scan_tiles(n);
   L.head = take(n ? 1 + PREFIX_MAX : 0);                  // the domain byte 0x00 and the prefix
   L.pos = take(n * sizeof(uint32_t));                     // 1 = ballot b has a leaf, then its rank
   L.tiles = take((size_t)L.n_tiles * sizeof(uint32_t));

@@ -222,10 +222,12 @@ EG_HD uint32_t merkle_lane_check(const Mem& m, uint64_t j, uint64_t n_leaves) {
 
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
+#include "scan.cuh"
 
 namespace eg {
 
 constexpr int MERKLE_NT = 256;
+static_assert(MERKLE_NT == SCAN_NT, "the scan kernels are launched with MERKLE_NT lanes");
 
 __device__ __forceinline__ void merkle_ld8(u32 w[8], const u32* p) {
 #pragma unroll
@@ -272,34 +274,19 @@ __global__ void __launch_bounds__(MERKLE_NT) k_merkle_leaf(MerkleLeafDev mem, co
   merkle_lane_leaf(mem, b, !status || status[b] == 0u);
 }
 
-// ---- exclusive prefix sum of the keep flags (three launches, as k_weed_scan_* and k_roll_scan_*) ----------------------------------------
+// ---- exclusive prefix sum of the keep flags (three launches: scan.cuh) ------------------------------------------------------------------
+struct MerkleKeepLoad {
+  const u32* pos; u32 n;
+  __device__ __forceinline__ void operator()(u32 v[1], u32 i) const { v[0] = i < n ? pos[i] : 0u; }
+};
 __global__ void __launch_bounds__(MERKLE_NT) k_merkle_scan_tiles(const u32* pos, u32 n, u32* tile_sums) {
-  __shared__ u32 red[MERKLE_NT / 64];
-  u32 x = 0;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const u32 i = blockIdx.x * egm::SCAN_TILE + threadIdx.x * 4u + e;
-    x += i < n ? pos[i] : 0u;
-  }
-  for (int off = 32; off >= 1; off >>= 1) x += (u32)__shfl_down((int)x, off, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = x;
-  __syncthreads();
-  if (threadIdx.x == 0) tile_sums[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+  scan_tile_sums<1>(tile_sums, MerkleKeepLoad{pos, n});
 }
 // one wavefront: tile sums -> exclusive prefix sums; the total, whether the leaves fit the log, the new count, the found words
 __global__ void k_merkle_scan_tops(u32 n_tiles, u32* tile_sums, uint64_t n_prior, uint64_t room, u32* total_word, unsigned long long* log_count,
                                    u32* found) {
-  const int lane = threadIdx.x & 63;
-  u32 run = 0;
-  for (u32 b0 = 0; b0 < n_tiles; b0 += 64) {
-    const u32 b = b0 + lane;
-    const u32 v = b < n_tiles ? tile_sums[b] : 0u;
-    u32 x = v;
-    for (int off = 1; off < 64; off <<= 1) { const u32 y = (u32)__shfl_up((int)x, off, 64); if (lane >= off) x += y; }
-    if (b < n_tiles) tile_sums[b] = run + x - v;
-    run += (u32)__shfl((int)x, 63, 64);
-  }
-  if (lane == 0) {
+  const u32 run = scan_tops<1>(n_tiles, tile_sums);
+  if ((threadIdx.x & 63) == 0) {
     const bool fits = !log_count || run <= room;
     if (total_word) { total_word[0] = run; total_word[1] = fits ? 1u : 0u; }       // null: a call without ballots
     if (log_count) *log_count = n_prior + (fits ? run : 0u);
@@ -308,28 +295,13 @@ __global__ void k_merkle_scan_tops(u32 n_tiles, u32* tile_sums, uint64_t n_prior
 }
 // pos[b]: keep flag -> rank among the ballots with a leaf, NO_PATH for the others
 __global__ void __launch_bounds__(MERKLE_NT) k_merkle_scan_apply(u32* pos, u32 n, const u32* tile_sums) {
-  __shared__ u32 part[MERKLE_NT];
-  u32 v[4], sum = 0;
+  u32 v[SCAN_PER_LANE][1], run[1];
+  scan_apply<1>(tile_sums, MerkleKeepLoad{pos, n}, v, run);
 #pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const u32 i = blockIdx.x * egm::SCAN_TILE + threadIdx.x * 4u + e;
-    v[e] = i < n ? pos[i] : 0u;
-    sum += v[e];
-  }
-  part[threadIdx.x] = sum;
-  __syncthreads();
-  for (int d = 1; d < MERKLE_NT; d <<= 1) {       // Hillis-Steele inclusive scan over the 256 lanes
-    const u32 add = (int)threadIdx.x >= d ? part[threadIdx.x - d] : 0u;
-    __syncthreads();
-    part[threadIdx.x] += add;
-    __syncthreads();
-  }
-  u32 run = tile_sums[blockIdx.x] + (threadIdx.x ? part[threadIdx.x - 1] : 0u);
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const u32 i = blockIdx.x * egm::SCAN_TILE + threadIdx.x * 4u + e;
-    if (i < n) pos[i] = v[e] ? run : egm::NO_PATH;
-    run += v[e];
+  for (int e = 0; e < SCAN_PER_LANE; ++e) {
+    const u32 i = scan_element(e);
+    if (i < n) pos[i] = v[e][0] ? run[0] : egm::NO_PATH;
+    run[0] += v[e][0];
   }
 }
 struct MerklePlaceDev {

@@ -22,8 +22,11 @@
 // Floor: the c w doublings of the top window are the same ~0.4 ms of one lane that bound every other schedule.
 #pragma once
 #include "kernels.cuh"
+#include "scan.cuh"
 
 namespace eg {
+
+static_assert(NT == SCAN_NT, "the scan kernels here and in group_tally_kernels.cuh are launched with NT lanes");
 
 constexpr int PIP_SEG = 16;            // buckets per lane of k_pip_window
 constexpr int PIP_NIELS_WORDS = 24;    // (y + x, y - x, 2dxy), 256 bits each
@@ -119,7 +122,7 @@ __global__ void __launch_bounds__(NT, 2) k_pip_prepare(size_t terms, int c, cons
 
 // ---- prefix sums over the buckets, for the term lists and for every level of pieces at once -------------------------------------------------------
 // Sequence 0 = counts (-> list offsets); sequence l + 1 = pieces of level l: ceil(counts / 128), then ceil(. / 64) of the level before.
-// Three launches: sums of tiles of 1024 buckets, an exclusive scan of the tile sums by one block, the scan inside every tile.
+// Three launches (scan.cuh): sums of tiles of buckets, an exclusive scan of the tile sums by one block, the scan inside every tile.
 constexpr int PIP_SEQ = 6;             // offsets + up to 5 levels
 struct PipScan { u32* offsets; u32* pieces[PIP_SEQ - 1]; u32* piece0[PIP_SEQ - 1]; u32* totals; u32* cursors; u32* tile_sums; };
 __device__ __forceinline__ void pip_tuple(u32 v[PIP_SEQ], u32 cnt, int levels) {
@@ -128,67 +131,24 @@ __device__ __forceinline__ void pip_tuple(u32 v[PIP_SEQ], u32 cnt, int levels) {
 #pragma unroll
   for (int l = 0; l < PIP_SEQ - 1; ++l) { v[l + 1] = l < levels ? m : 0u; m = (m + PIP_S_POINTS - 1u) / PIP_S_POINTS; }
 }
+struct PipLoad {
+  const u32* counts; u32 n; int levels;
+  __device__ __forceinline__ void operator()(u32 v[PIP_SEQ], u32 i) const { pip_tuple(v, i < n ? counts[i] : 0u, levels); }
+};
 __global__ void __launch_bounds__(NT) k_pip_scan_tiles(const u32* counts, u32 n, int levels, PipScan S) {
-  __shared__ u32 red[PIP_SEQ][NT / 64];
-  u32 sum[PIP_SEQ] = {0, 0, 0, 0, 0, 0};
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const u32 i = blockIdx.x * 1024u + threadIdx.x * 4u + e;
-    u32 v[PIP_SEQ];
-    pip_tuple(v, i < n ? counts[i] : 0u, levels);
-#pragma unroll
-    for (int k = 0; k < PIP_SEQ; ++k) sum[k] += v[k];
-  }
-#pragma unroll
-  for (int k = 0; k < PIP_SEQ; ++k) {
-    u32 x = sum[k];
-    for (int off = 32; off >= 1; off >>= 1) x += (u32)__shfl_down((int)x, off, 64);
-    if ((threadIdx.x & 63) == 0) red[k][threadIdx.x >> 6] = x;
-  }
-  __syncthreads();
-  if (threadIdx.x < PIP_SEQ) S.tile_sums[blockIdx.x * PIP_SEQ + threadIdx.x] = red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3];
+  scan_tile_sums<PIP_SEQ>(S.tile_sums, PipLoad{counts, n, levels});
 }
-__global__ void k_pip_scan_tops(u32 n_tiles, PipScan S) {          // one wavefront per sequence: tile sums -> exclusive prefix sums, totals
-  const int k = threadIdx.x >> 6, lane = threadIdx.x & 63;           // launched with 64 * PIP_SEQ threads
-  u32 run = 0;
-  for (u32 b0 = 0; b0 < n_tiles; b0 += 64) {
-    const u32 b = b0 + lane;
-    const u32 v = b < n_tiles ? S.tile_sums[b * PIP_SEQ + k] : 0u;
-    u32 x = v;
-    for (int off = 1; off < 64; off <<= 1) { const u32 y = (u32)__shfl_up((int)x, off, 64); if (lane >= off) x += y; }
-    if (b < n_tiles) S.tile_sums[b * PIP_SEQ + k] = run + x - v;
-    run += (u32)__shfl((int)x, 63, 64);
-  }
-  if (lane == 0 && k >= 1) S.totals[k - 1] = run;
+__global__ void k_pip_scan_tops(u32 n_tiles, PipScan S) {          // launched with 64 * PIP_SEQ threads
+  const u32 total = scan_tops<PIP_SEQ>(n_tiles, S.tile_sums);
+  const int k = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0 && k >= 1) S.totals[k - 1] = total;
 }
 __global__ void __launch_bounds__(NT) k_pip_scan_apply(const u32* counts, u32 n, int levels, PipScan S) {
-  __shared__ u32 part[PIP_SEQ][NT];
-  u32 v[4][PIP_SEQ], sum[PIP_SEQ] = {0, 0, 0, 0, 0, 0};
+  u32 v[SCAN_PER_LANE][PIP_SEQ], run[PIP_SEQ];
+  scan_apply<PIP_SEQ>(S.tile_sums, PipLoad{counts, n, levels}, v, run);
 #pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const u32 i = blockIdx.x * 1024u + threadIdx.x * 4u + e;
-    pip_tuple(v[e], i < n ? counts[i] : 0u, levels);
-#pragma unroll
-    for (int k = 0; k < PIP_SEQ; ++k) sum[k] += v[e][k];
-  }
-#pragma unroll
-  for (int k = 0; k < PIP_SEQ; ++k) part[k][threadIdx.x] = sum[k];
-  __syncthreads();
-  for (int d = 1; d < NT; d <<= 1) {              // Hillis-Steele inclusive scan over the 256 lanes, all sequences together
-    u32 add[PIP_SEQ];
-#pragma unroll
-    for (int k = 0; k < PIP_SEQ; ++k) add[k] = (int)threadIdx.x >= d ? part[k][threadIdx.x - d] : 0u;
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < PIP_SEQ; ++k) part[k][threadIdx.x] += add[k];
-    __syncthreads();
-  }
-  u32 run[PIP_SEQ];
-#pragma unroll
-  for (int k = 0; k < PIP_SEQ; ++k) run[k] = S.tile_sums[blockIdx.x * PIP_SEQ + k] + (threadIdx.x ? part[k][threadIdx.x - 1] : 0u);
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const u32 i = blockIdx.x * 1024u + threadIdx.x * 4u + e;
+  for (int e = 0; e < SCAN_PER_LANE; ++e) {
+    const u32 i = scan_element(e);
     if (i < n) {
       S.offsets[i] = run[0];
       S.cursors[i] = 0u;

@@ -10,6 +10,7 @@
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+#include "scan_host.hpp"
 
 #if defined(__HIPCC__)
 #define EGR_HD __host__ __device__ inline
@@ -30,7 +31,6 @@ constexpr uint32_t GROUP_NONE = 0xffffffffu;      // EG_GROUP_NONE
 constexpr uint64_t N_LIMIT = 1ull << 31;          // n must stay below
 constexpr uint64_t KEYS_MAX = 1ull << 31;         // EG_ROLL_KEYS_MAX
 constexpr uint64_t SEQ_END_MAX = (1ull << 63) - 1; // seq_base + n may reach it
-constexpr uint32_t SCAN_TILE = 1024;              // ballots per block of the scan kernels
 
 EGR_HD uint64_t word_of(uint64_t seq, int policy) { return policy == ROLL_LAST ? seq + 1u : SEQ_END_MAX - seq; }
 EGR_HD uint64_t seq_of(uint64_t word, int policy) { return policy == ROLL_LAST ? word - 1u : SEQ_END_MAX - word; }
@@ -69,7 +69,7 @@ inline Layout layout(size_t n, size_t n_keys) {
   Layout L;
   size_t off = 0;
   auto take = [&](size_t bytes) { const size_t at = off; off += (bytes + 255) / 256 * 256; return at; };
-  L.n_tiles = (uint32_t)((n + SCAN_TILE - 1) / SCAN_TILE);
+  L.n_tiles = egscan::scan_tiles(n);
   L.best = take(n ? n_keys * sizeof(uint32_t) : 0);       // the largest claim on every voter, 0 = none
   L.flag = take(n * sizeof(uint32_t));                    // what the commit does for ballot b: FLAG_*, then FLAG_DISPLACED + rank
   L.tiles = take((size_t)L.n_tiles * sizeof(uint32_t));

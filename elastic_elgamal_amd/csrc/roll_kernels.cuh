@@ -115,10 +115,12 @@ inline uint32_t scan_displaced(uint32_t* flag, size_t n) {
 
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
+#include "scan.cuh"
 
 namespace eg {
 
 constexpr int ROLL_NT = 256;
+static_assert(ROLL_NT == SCAN_NT, "the scan kernels are launched with ROLL_NT lanes");
 
 struct RollMemDev {
   const uint32_t* index;
@@ -207,57 +209,27 @@ __global__ void __launch_bounds__(ROLL_NT) k_roll_check(RollMemDev mem, const ui
   roll_wave_tally(found + 2, V.off_roll);
 }
 
-// ---- exclusive prefix sum of the displaced flags (three launches, as k_weed_scan_*) ------------------------------------------------------
-__device__ __forceinline__ uint32_t roll_is_displaced(const uint32_t* flag, uint32_t i, uint32_t n) {
-  return i < n && flag[i] == egr::FLAG_DISPLACED ? 1u : 0u;
-}
+// ---- exclusive prefix sum of the displaced flags (three launches: scan.cuh) ----------------------------------------------------------------
+struct RollDisplacedLoad {
+  const uint32_t* flag; uint32_t n;
+  __device__ __forceinline__ void operator()(uint32_t v[1], uint32_t i) const { v[0] = i < n && flag[i] == egr::FLAG_DISPLACED ? 1u : 0u; }
+};
 __global__ void __launch_bounds__(ROLL_NT) k_roll_scan_tiles(const uint32_t* flag, uint32_t n, uint32_t* tile_sums) {
-  __shared__ uint32_t red[ROLL_NT / 64];
-  uint32_t x = 0;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) x += roll_is_displaced(flag, blockIdx.x * egr::SCAN_TILE + threadIdx.x * 4u + e, n);
-  for (int off = 32; off >= 1; off >>= 1) x += (uint32_t)__shfl_down((int)x, off, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = x;
-  __syncthreads();
-  if (threadIdx.x == 0) tile_sums[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+  scan_tile_sums<1>(tile_sums, RollDisplacedLoad{flag, n});
 }
 // one wavefront: tile sums -> exclusive prefix sums; the total is the number of displaced entries
 __global__ void k_roll_scan_tops(uint32_t n_tiles, uint32_t* tile_sums, unsigned long long* displaced_count) {
-  const int lane = threadIdx.x & 63;
-  uint32_t run = 0;
-  for (uint32_t b0 = 0; b0 < n_tiles; b0 += 64) {
-    const uint32_t b = b0 + lane;
-    const uint32_t v = b < n_tiles ? tile_sums[b] : 0u;
-    uint32_t x = v;
-    for (int off = 1; off < 64; off <<= 1) { const uint32_t y = (uint32_t)__shfl_up((int)x, off, 64); if (lane >= off) x += y; }
-    if (b < n_tiles) tile_sums[b] = run + x - v;
-    run += (uint32_t)__shfl((int)x, 63, 64);
-  }
-  if (lane == 0) *displaced_count = run;
+  const uint32_t run = scan_tops<1>(n_tiles, tile_sums);
+  if ((threadIdx.x & 63) == 0) *displaced_count = run;
 }
 // flag[b]: FLAG_DISPLACED -> FLAG_DISPLACED + rank among the displaced ones; the other words stay
 __global__ void __launch_bounds__(ROLL_NT) k_roll_scan_apply(uint32_t* flag, uint32_t n, const uint32_t* tile_sums) {
-  __shared__ uint32_t part[ROLL_NT];
-  uint32_t v[4], sum = 0;
+  uint32_t v[SCAN_PER_LANE][1], run[1];
+  scan_apply<1>(tile_sums, RollDisplacedLoad{flag, n}, v, run);
 #pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    v[e] = roll_is_displaced(flag, blockIdx.x * egr::SCAN_TILE + threadIdx.x * 4u + e, n);
-    sum += v[e];
-  }
-  part[threadIdx.x] = sum;
-  __syncthreads();
-  for (int d = 1; d < ROLL_NT; d <<= 1) {         // Hillis-Steele inclusive scan over the 256 lanes
-    const uint32_t add = (int)threadIdx.x >= d ? part[threadIdx.x - d] : 0u;
-    __syncthreads();
-    part[threadIdx.x] += add;
-    __syncthreads();
-  }
-  uint32_t run = tile_sums[blockIdx.x] + (threadIdx.x ? part[threadIdx.x - 1] : 0u);
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const uint32_t i = blockIdx.x * egr::SCAN_TILE + threadIdx.x * 4u + e;
-    if (v[e]) flag[i] = egr::FLAG_DISPLACED + run;
-    run += v[e];
+  for (int e = 0; e < SCAN_PER_LANE; ++e) {
+    if (v[e][0]) flag[scan_element(e)] = egr::FLAG_DISPLACED + run[0];           // (set only below n)
+    run[0] += v[e][0];
   }
 }
 __global__ void __launch_bounds__(ROLL_NT) k_roll_commit(RollMemDev mem, const uint32_t* flag, uint64_t n, uint64_t seq_base, int policy,

@@ -11,6 +11,7 @@
 #include <stddef.h>
 #include <stdint.h>
 #include <vector>
+#include "scan_host.hpp"
 
 #if defined(__HIPCC__)
 #define EGW_HD __host__ __device__ inline
@@ -28,7 +29,6 @@ constexpr uint64_t KEYS_MAX = 1ull << 30;         // EG_WEED_KEYS_MAX: n K + n_p
 constexpr uint64_t EMPTY = ~0ull;
 constexpr uint64_t BATCH_BASE = 1ull << 32;
 constexpr uint64_t MIN_SLOTS = 1024;
-constexpr uint32_t SCAN_TILE = 1024;              // ballots per block of the scan kernels
 constexpr size_t KEY_BYTES = 64;
 
 EGW_HD uint64_t board_ref(uint64_t j) { return j; }
@@ -81,7 +81,7 @@ inline Layout layout(size_t n, size_t n_prior, uint32_t keys_per_ballot) {
   size_t off = 0;
   auto take = [&](size_t bytes) { const size_t at = off; off += (bytes + 255) / 256 * 256; return at; };
   L.slots = n ? table_slots((uint64_t)n * keys_per_ballot + n_prior) : 0;
-  L.n_tiles = (uint32_t)((n + SCAN_TILE - 1) / SCAN_TILE);
+  L.n_tiles = egscan::scan_tiles(n);
   L.table = take((size_t)L.slots * sizeof(uint64_t));
   L.pos = take(n * sizeof(uint32_t));                     // keep flag of every ballot, then its rank among the kept ones
   L.tiles = take((size_t)L.n_tiles * sizeof(uint32_t));

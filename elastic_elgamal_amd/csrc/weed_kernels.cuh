@@ -113,10 +113,12 @@ EGW_HD bool append_fits(uint64_t n_prior, uint32_t kept, uint32_t keys_per_ballo
 
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
+#include "scan.cuh"
 
 namespace eg {
 
 constexpr int WEED_NT = 256;
+static_assert(WEED_NT == SCAN_NT, "the scan kernels are launched with WEED_NT lanes");
 
 struct WeedTableDev {
   unsigned long long* slots;
@@ -193,34 +195,19 @@ __global__ void __launch_bounds__(WEED_NT) k_weed_lookup(WeedKeysDev keys, const
   weed_wave_tally(found + 2, missing);
 }
 
-// ---- exclusive prefix sum of the keep flags (three launches, as k_gt_scan_*) -------------------------------------------------------------
+// ---- exclusive prefix sum of the keep flags (three launches: scan.cuh) --------------------------------------------------------------------
+struct WeedKeepLoad {
+  const uint32_t* pos; uint32_t n;
+  __device__ __forceinline__ void operator()(uint32_t v[1], uint32_t i) const { v[0] = i < n ? pos[i] : 0u; }
+};
 __global__ void __launch_bounds__(WEED_NT) k_weed_scan_tiles(const uint32_t* pos, uint32_t n, uint32_t* tile_sums) {
-  __shared__ uint32_t red[WEED_NT / 64];
-  uint32_t x = 0;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const uint32_t i = blockIdx.x * egw::SCAN_TILE + threadIdx.x * 4u + e;
-    x += i < n ? pos[i] : 0u;
-  }
-  for (int off = 32; off >= 1; off >>= 1) x += (uint32_t)__shfl_down((int)x, off, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = x;
-  __syncthreads();
-  if (threadIdx.x == 0) tile_sums[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+  scan_tile_sums<1>(tile_sums, WeedKeepLoad{pos, n});
 }
 // one wavefront: tile sums -> exclusive prefix sums; the total, whether the kept keys fit the board, the new board count
 __global__ void k_weed_scan_tops(uint32_t n_tiles, uint32_t* tile_sums, uint32_t keys_per_ballot, uint64_t n_prior, uint64_t board_cap,
                                  uint32_t* total_word, unsigned long long* board_count, uint32_t* found) {
-  const int lane = threadIdx.x & 63;
-  uint32_t run = 0;
-  for (uint32_t b0 = 0; b0 < n_tiles; b0 += 64) {
-    const uint32_t b = b0 + lane;
-    const uint32_t v = b < n_tiles ? tile_sums[b] : 0u;
-    uint32_t x = v;
-    for (int off = 1; off < 64; off <<= 1) { const uint32_t y = (uint32_t)__shfl_up((int)x, off, 64); if (lane >= off) x += y; }
-    if (b < n_tiles) tile_sums[b] = run + x - v;
-    run += (uint32_t)__shfl((int)x, 63, 64);
-  }
-  if (lane == 0) {
+  const uint32_t run = scan_tops<1>(n_tiles, tile_sums);
+  if ((threadIdx.x & 63) == 0) {
     const bool fits = egw::append_fits(n_prior, run, keys_per_ballot, board_cap);
     if (total_word) { total_word[0] = run; total_word[1] = fits ? 1u : 0u; }
     *board_count = n_prior + (fits ? (uint64_t)run * keys_per_ballot : 0u);
@@ -229,28 +216,13 @@ __global__ void k_weed_scan_tops(uint32_t n_tiles, uint32_t* tile_sums, uint32_t
 }
 // pos[b]: keep flag -> rank among the kept ballots, 0xffffffff for the others
 __global__ void __launch_bounds__(WEED_NT) k_weed_scan_apply(uint32_t* pos, uint32_t n, const uint32_t* tile_sums) {
-  __shared__ uint32_t part[WEED_NT];
-  uint32_t v[4], sum = 0;
+  uint32_t v[SCAN_PER_LANE][1], run[1];
+  scan_apply<1>(tile_sums, WeedKeepLoad{pos, n}, v, run);
 #pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const uint32_t i = blockIdx.x * egw::SCAN_TILE + threadIdx.x * 4u + e;
-    v[e] = i < n ? pos[i] : 0u;
-    sum += v[e];
-  }
-  part[threadIdx.x] = sum;
-  __syncthreads();
-  for (int d = 1; d < WEED_NT; d <<= 1) {         // Hillis-Steele inclusive scan over the 256 lanes
-    const uint32_t add = (int)threadIdx.x >= d ? part[threadIdx.x - d] : 0u;
-    __syncthreads();
-    part[threadIdx.x] += add;
-    __syncthreads();
-  }
-  uint32_t run = tile_sums[blockIdx.x] + (threadIdx.x ? part[threadIdx.x - 1] : 0u);
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const uint32_t i = blockIdx.x * egw::SCAN_TILE + threadIdx.x * 4u + e;
-    if (i < n) pos[i] = v[e] ? run : 0xffffffffu;
-    run += v[e];
+  for (int e = 0; e < SCAN_PER_LANE; ++e) {
+    const uint32_t i = scan_element(e);
+    if (i < n) pos[i] = v[e][0] ? run[0] : 0xffffffffu;
+    run[0] += v[e][0];
   }
 }
 // lanes: ballots x keys x 4 quarters of 16 bytes.  Nothing is written unless everything fits

@@ -331,6 +331,39 @@ def test_leaf_pass_against_hashlib(torch, eg, ctx, elections, kind, n):
     assert eg.ReceiptLog(ctx).leaves(msgs, size).leaves == b"".join(M.leaf_hash(m) for m in items)
 
 
+_seam_batches = {}
+
+
+def seam_batch(n):
+    """(messages, status words, leaves, the model's pass with exact room, with one entry less) - computed once per size, left unchanged"""
+    if n not in _seam_batches:
+        msgs = np.random.default_rng(n).integers(0, 256, 8 * n, dtype=np.uint8).tobytes()
+        status = [0] * n
+        for lane in (0, 1023, 1024, 65535, 65536, n - 1):
+            if lane < n:
+                status[lane] = 6 | (lane << 8)
+        items = [msgs[8 * b:8 * b + 8] for b in range(n)]
+        kept = status.count(0)
+        _seam_batches[n] = (msgs, status, kept, M.leaves_pass(items, b"", None, status, 0, kept), M.leaves_pass(items, b"", None, status, 0, kept - 1))
+    return _seam_batches[n]
+
+
+@pytest.mark.parametrize("n", [TILE + 1, 65 * TILE + 1])
+def test_leaf_pass_at_the_seams_of_the_scan(torch, eg, ctx, n):
+    """the ranks across a tile of the scan (1024 ballots) and across the second round of its tile sums (64 tiles): 8-byte messages, rejected
+    ballots on both sides of every seam and at the end; a log with room for exactly the leaves takes them all, one entry less takes none"""
+    msgs, status, kept, want_fit, want_short = seam_batch(n)
+    d_msgs = dev(torch, msgs)
+    got = leaves_dev(torch, eg, ctx, d_msgs, n, 8, status=status, log=b"", log_cap=kept)
+    same_leaves(got, want_fit, b"", kept)
+    last = max(b for b in range(n) if status[b] == 0)
+    assert got["found"] == [kept, 0] and got["log_count"] == kept and got["leaf_index"][last] == kept - 1
+    got = leaves_dev(torch, eg, ctx, d_msgs, n, 8, status=status, log=b"", log_cap=kept - 1)
+    same_leaves(got, want_short, b"", kept - 1)
+    assert got["found"] == [kept, 1] and got["log_count"] == 0 and got["log"] == bytes([0xA7]) * (32 * (kept - 1))
+    assert tail_ok(d_msgs, 8 * n)
+
+
 def test_two_batches_through_one_log_and_the_append_that_does_not_fit(torch, eg, ctx, elections):
     p = elections["single"]
     size = p.ballot_size

@@ -128,10 +128,10 @@ def check_against_model(torch, shape, arr, status=None, board=(), **kw):
 
 
 # ------------------------------------------------------------------ sizes and lanes
-@pytest.mark.parametrize("n", [1, 63, 64, 65, 257])
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 257, 1025])
 def test_copies_at_the_seams_of_wavefronts_and_blocks(torch, single5, n):
     """the copy at lanes 0, 63, 64 and last: against the board (the only way ballot 0 is flagged), as a copy of the first ballot, and as
-    the original of the last ballot"""
+    the original of the last ballot; with 1025 ballots, a copy and an append across the first tile of the scan over the keep flags"""
     board = [bytes(np.random.default_rng(99).integers(0, 256, 64, dtype=np.uint8))]
     for at in sorted({0, 63, 64, n - 1}):
         if at >= n:
@@ -153,6 +153,12 @@ def test_copies_at_the_seams_of_wavefronts_and_blocks(torch, single5, n):
     arr = single5.random_ballots(n, n)
     _, dup, _, _ = check_against_model(torch, single5, arr)
     assert dup == [NONE] * n
+    if n > 1024:                                                          # ballot 1024 copies ballot 1023; the kept keys go out in ballot order
+        arr[1024] = arr[1023]
+        _, _, appended = W.weed(single5.keys(arr), None, [])
+        got, dup, _, _ = check_against_model(torch, single5, arr, board_cap=len(appended), append=True)
+        assert dup[1024] == 1023 and dup.count(NONE) == n - 1
+        assert got["count"] == len(appended) == 5 * (n - 1) and got["board"] == b"".join(appended) and got["found"][2] == 0
 
 
 def test_4096_identical_ballots(torch, single5):
