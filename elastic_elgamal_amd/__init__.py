@@ -203,6 +203,16 @@ def _load() -> C.CDLL:
         "eg_qv_weed_scratch_bytes": (sz, [vp, sz, sz]),
         "eg_qv_weed_device": (C.c_int, [vp, sz, vp, vp, sz, vp, sz, C.c_uint64, vp, vp, vp, vp, vp, vp]),
         "eg_qv_weed": (C.c_int, [vp, sz, vp, vp, sz, vp, vp, vp, vp, C.POINTER(sz)]),
+        "eg_choice_open_check_scratch_bytes": (sz, [vp, sz]),
+        "eg_choice_open_check_device": (C.c_int, [vp, sz, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "eg_choice_open_check": (C.c_int, [vp, sz, vp, vp, vp, vp, vp, vp]),
+        "eg_qv_open_check_scratch_bytes": (sz, [vp, sz]),
+        "eg_qv_open_check_device": (C.c_int, [vp, sz, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "eg_qv_open_check": (C.c_int, [vp, sz, vp, vp, vp, vp, vp, vp]),
+        "eg_choice_open_batch_device": (C.c_int, [vp, C.c_uint64, sz, sz, C.c_int, C.c_uint64, vp, vp, vp, vp]),
+        "eg_choice_open_batch": (C.c_int, [vp, C.c_uint64, sz, sz, C.c_int, C.c_uint64, vp, vp, vp]),
+        "eg_qv_open_batch_device": (C.c_int, [vp, C.c_uint64, sz, sz, C.c_uint64, vp, vp, vp, vp]),
+        "eg_qv_open_batch": (C.c_int, [vp, C.c_uint64, sz, sz, C.c_uint64, vp, vp, vp]),
         "eg_ed25519_verify_scratch_bytes": (sz, [vp, sz]),
         "eg_ed25519_verify_device": (C.c_int, [vp, sz, vp, sz, sz, cp, sz, vp, sz, vp, vp, vp, vp, vp, sz, vp]),
         "eg_ed25519_verify_batch": (C.c_int, [vp, sz, cp, sz, sz, cp, sz, cp, sz, vp, cp, vp, vp]),
@@ -313,6 +323,16 @@ ROLL_FIRST, ROLL_LAST = 1, 2     # include/eg_hip.h: EG_ROLL_FIRST / EG_ROLL_LAS
 ROLL_SUPERSEDED, ROLL_OFF_ROLL, ROLL_NOT_CAST = 1, 2, 3
 SEQ_NONE = (1 << 64) - 1         # include/eg_hip.h: EG_SEQ_NONE
 ROLL_KEYS_MAX = 1 << 31          # include/eg_hip.h: EG_ROLL_KEYS_MAX
+ST_BAD_OPENING = 17              # include/eg_hip.h: EG_ST_BAD_OPENING, what open_check writes; the detail is open_detail(slot, check)
+OPEN_BAD_SCALAR, OPEN_R, OPEN_B = 1, 2, 3    # include/eg_hip.h: EG_OPEN_*, the check of an opening that failed
+OPEN_ITEMS_MAX = 1 << 31         # include/eg_hip.h: EG_OPEN_ITEMS_MAX
+
+
+def open_detail(slot: int, check: int) -> int:
+    """EG_OPEN_DETAIL: the detail of a status word of kind ST_BAD_OPENING; slot = detail >> 2, check = detail & 3."""
+    return slot * 4 + check
+
+
 MERKLE_BAD_INDEX, MERKLE_BAD_LENGTH, MERKLE_MISMATCH = 1, 2, 3    # include/eg_hip.h: EG_MERKLE_*, the verdict of a receipt
 MERKLE_MISMATCH_OLD = 4          # include/eg_hip.h: EG_MERKLE_MISMATCH_OLD, a consistency proof that does not give the old root
 MERKLE_HASH_BYTES = 32           # include/eg_hip.h: EG_MERKLE_HASH_BYTES
@@ -1391,6 +1411,52 @@ class _BatchParams:
                                         hash_seed & 0xFFFFFFFFFFFFFFFF, d_scratch or None, d_dup_of or None, d_status_out or None,
                                         d_board_count or None, d_found or None, stream or None))
 
+    def open_check_scratch_bytes(self, n: int) -> int:
+        """Device scratch that open_check_device needs for n opened ballots (0 for arguments it refuses)."""
+        return int(self._fn("open_check_scratch_bytes")(self._h, n))
+
+    def open_check(self, ballots: bytes, values, rand: bytes, status_in=None):
+        """Ballot audit (eg_*_open_check; include/eg_hip.h, "ballot audits" has the rule): do the opened ballots encrypt what their
+        openings say.  values = n x n_options integers below 2**64 and rand = n x n_options x 32 bytes, the value and the encryption
+        randomness of every tally ciphertext in ballot and then slot order.  Returns (status_out, found): status_out[b] = 0, the word
+        of status_in for a ballot that does not participate, or ST_BAD_OPENING with open_detail(slot, check) as its detail; found =
+        [ballots that participated, ballots that failed].  An opened ballot must never be counted: put its ciphertexts onto
+        weeding's board (weed(..., append=True) over the audited pile)."""
+        n = len(ballots) // self.ballot_size
+        if n * self.ballot_size != len(ballots):
+            raise ValueError("ballots is not a whole number of packed ballots")
+        values = list(values)
+        if len(values) != n * self.n_options or len(rand) != 32 * n * self.n_options:
+            raise ValueError("values and rand need one entry per ballot and option")
+        if any(not 0 <= int(v) < 1 << 64 for v in values):
+            raise ValueError("a value is outside 0 .. 2^64 - 1")
+        sin = None
+        if status_in is not None:
+            status_in = list(status_in)
+            if len(status_in) != n:
+                raise ValueError("status_in needs one word per ballot")
+            sin = (C.c_uint32 * max(n, 1))(*status_in)
+        buf = (C.c_char * max(len(ballots), 1)).from_buffer_copy(ballots or b"\0")
+        val = (C.c_uint64 * max(len(values), 1))(*values)
+        rnd = (C.c_char * max(len(rand), 1)).from_buffer_copy(rand or b"\0")
+        out, found = (C.c_uint32 * max(n, 1))(), (C.c_uint32 * 2)()
+        _check(self._fn("open_check")(self._h, n, buf, sin, val, rnd, out, found))
+        return list(out[:n]), list(found)
+
+    def open_check_device(self, n: int, d_ballots: int, d_values: int, d_rand: int, d_status_out: int, d_found: int, d_scratch: int,
+                          d_status_in: int = 0, stream: int = 0):
+        """Asynchronous device-pointer variant (eg_*_open_check_device): no allocation, no host synchronisation, no lock.  d_values: n x
+        n_options uint64; d_rand: n x n_options x 32 bytes; d_status_out: n uint32, may be d_status_in; d_found: two uint32 the
+        library writes; d_scratch: open_check_scratch_bytes(n) bytes."""
+        _check(self._fn("open_check_device")(self._h, n, d_ballots or None, d_status_in or None, d_values or None, d_rand or None,
+                                              d_status_out or None, d_found or None, d_scratch or None, stream or None))
+
+    def _open_batch(self, n: int, call):
+        values = (C.c_uint64 * max(n * self.n_options, 1))()
+        rand = C.create_string_buffer(max(32 * n * self.n_options, 1))
+        _check(call(values, rand))
+        return list(values[: n * self.n_options]), rand.raw[: 32 * n * self.n_options]
+
 
 class ChoiceParams(_BatchParams):
     """``ChoiceParams::single(pk, n)`` / ``::multi(pk, n)`` (choice.rs:160-196)."""
@@ -1438,6 +1504,26 @@ class ChoiceParams(_BatchParams):
         out = C.create_string_buffer(max(n * self.ballot_size, 1))
         _check(_load().eg_choice_encrypt_selected_batch(self._h, base_seed, first, n, rng_skip, arr, out))
         return out.raw[: n * self.ballot_size]
+
+    def open_batch(self, base_seed: int, first: int, n: int, selections=None, rng_skip: int = 0, n_selected: int = 0):
+        """The opener (eg_choice_open_batch; VARIABLE TIME, test and benchmark openings only): (values, rand) of the ballots that
+        encrypt_selected(base_seed, first, selections, rng_skip) makes or, with `selections` None, encrypt_batch(base_seed, first, n,
+        n_selected) (rng_skip 0).  values = n x n_options integers (1 = chosen), rand = n x n_options x 32 bytes."""
+        arr = None
+        if selections is not None:
+            sel = list(selections)
+            if len(sel) != n:
+                raise ValueError("selections needs one bitmask per ballot")
+            sw = (self.n_options + 31) // 32
+            words = [(int(m) >> (32 * w)) & 0xFFFFFFFF for m in sel for w in range(sw)]
+            arr = (C.c_uint32 * max(len(words), 1))(*words)
+        return self._open_batch(n, lambda v, r: _load().eg_choice_open_batch(self._h, base_seed, first, n, n_selected, rng_skip, arr, v, r))
+
+    def open_batch_device(self, base_seed: int, first: int, n: int, d_values_out: int, d_rand_out: int, d_selection: int = 0,
+                          rng_skip: int = 0, n_selected: int = 0, stream: int = 0):
+        """The opener on device buffers (eg_choice_open_batch_device): asynchronous on `stream`, no lock, no workspace."""
+        _check(_load().eg_choice_open_batch_device(self._h, base_seed, first, n, n_selected, rng_skip, d_selection or None,
+                                                   d_values_out or None, d_rand_out or None, stream or None))
 
     def close(self):
         if getattr(self, "_h", None):
@@ -1627,6 +1713,25 @@ class QuadraticVotingParams(_BatchParams):
         out = C.create_string_buffer(max(n * self.ballot_size, 1))
         _check(_load().eg_qv_encrypt_votes_batch(self._h, base_seed, first, n, rng_skip, arr, out))
         return out.raw[: n * self.ballot_size]
+
+    def open_batch(self, base_seed: int, first: int, n: int, votes=None, rng_skip: int = 0):
+        """The opener (eg_qv_open_batch; VARIABLE TIME, test and benchmark openings only): (values, rand) of the vote ciphertexts of
+        the ballots that encrypt_votes(base_seed, first, votes, rng_skip) makes or, with `votes` None, encrypt_batch_device(base_seed,
+        first, n) (rng_skip 0).  values = n x n_options votes, rand = n x n_options x 32 bytes."""
+        arr = None
+        if votes is not None:
+            votes = [list(v) for v in votes]
+            if len(votes) != n or any(len(v) != self.n_options for v in votes):
+                raise ValueError("every ballot needs n_options votes")
+            flat = [x for v in votes for x in v]
+            arr = (C.c_uint32 * max(len(flat), 1))(*flat)
+        return self._open_batch(n, lambda v, r: _load().eg_qv_open_batch(self._h, base_seed, first, n, rng_skip, arr, v, r))
+
+    def open_batch_device(self, base_seed: int, first: int, n: int, d_values_out: int, d_rand_out: int, d_votes: int = 0,
+                          rng_skip: int = 0, stream: int = 0):
+        """The opener on device buffers (eg_qv_open_batch_device): asynchronous on `stream`, no lock, no workspace."""
+        _check(_load().eg_qv_open_batch_device(self._h, base_seed, first, n, rng_skip, d_votes or None, d_values_out or None,
+                                               d_rand_out or None, stream or None))
 
     def close(self):
         if getattr(self, "_h", None):

@@ -1,5 +1,6 @@
 // eg_gen.hip -- translation unit of the synthetic-ballot generator kernels (prover_kernels.cuh).
 #include "prover_kernels.cuh"
+#include "open_gen_kernels.cuh"
 
 using namespace eg;
 
@@ -48,4 +49,14 @@ void eg_launch_share_prove(int blocks, hipStream_t s, u64 seed0, size_t n, u64 r
   for (int w = 0; w < 8; ++w) { key.secret[w] = secret[w]; key.participant_key[w] = participant_key[w]; }
   hipLaunchKernelGGL(k_share_prove, dim3(blocks), dim3(NT), 0, s, seed0, n, rng_skip, key, ct_random, tabG, prefixes, pre, out, ok,
                      reinterpret_cast<uint4*>(gws));
+}
+
+// ---- the opener (open_gen_kernels.cuh): values and encryption randomness of the ballots the two generators above make ----
+void eg_launch_choice_open(int blocks, hipStream_t s, u64 seed0, size_t n, int n_options, int single, int n_selected, const u32* selection,
+                           u64 rng_skip, unsigned long long* values, u32* rand) {
+  hipLaunchKernelGGL(k_choice_open, dim3(blocks), dim3(NT), 0, s, seed0, n, n_options, single, n_selected, selection, rng_skip, values, rand);
+}
+void eg_launch_qv_open(int blocks, hipStream_t s, u64 seed0, size_t n, int n_options, u64 credits, const u32* votes, u64 rng_skip,
+                       u64 draws_per_vote, unsigned long long* values, u32* rand) {
+  hipLaunchKernelGGL(k_qv_open, dim3(blocks), dim3(NT), 0, s, seed0, n, n_options, credits, votes, rng_skip, draws_per_vote, values, rand);
 }

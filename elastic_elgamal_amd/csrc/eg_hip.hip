@@ -38,6 +38,7 @@
 #include "roll_kernels.cuh"
 #include "merkle_kernels.cuh"
 #include "merkle_audit_kernels.cuh"
+#include "open_kernels.cuh"
 
 using namespace eg;
 
@@ -60,6 +61,10 @@ void eg_launch_sumsq_prove(int blocks, hipStream_t s, u64 seed0, size_t n, u64 r
                            const uint4* tabG, const uint4* tabK, const u32* prefixes, u32* out, u32 stride_words, u32* gws);
 void eg_launch_share_prove(int blocks, hipStream_t s, u64 seed0, size_t n, u64 rng_skip, const u32 secret[8], const u32 participant_key[8],
                            const u32* ct_random, const uint4* tabG, const u32* prefixes, int pre, u32* out, unsigned char* ok, u32* gws);
+void eg_launch_choice_open(int blocks, hipStream_t s, u64 seed0, size_t n, int n_options, int single, int n_selected, const u32* selection,
+                           u64 rng_skip, unsigned long long* values, u32* rand);
+void eg_launch_qv_open(int blocks, hipStream_t s, u64 seed0, size_t n, int n_options, u64 credits, const u32* votes, u64 rng_skip,
+                       u64 draws_per_vote, unsigned long long* values, u32* rand);
 unsigned eg_gen_choice_ws_words(int n_options);
 unsigned eg_gen_qv_ws_words(int n_options, unsigned max_rings, unsigned max_responses);
 
@@ -3745,6 +3750,35 @@ size_t eg_qv_ballot_size_for(int n_options, uint64_t credits) {
 }
 
 // ---- synthetic ballots ---------------------------------------------------------------------------------------------------------
+// what EncryptedChoice::single / ::new would refuse or mis-prove (the host forms of the generator and of the opener)
+static int check_selection(const eg_choice_params* p, size_t n, const uint32_t* selection) {
+  const size_t sw = ((size_t)p->n_options + 31) / 32;
+  for (size_t i = 0; i < n; ++i) {
+    int chosen = 0;
+    for (size_t w = 0; w < sw; ++w) {
+      const uint32_t word = selection[i * sw + w];
+      const int valid_bits = (int)std::min<size_t>(32, (size_t)p->n_options - 32 * w);
+      if (valid_bits < 32 && (word >> valid_bits)) return fail(EG_ERR_BAD_ARG, "selection has bits beyond the options");
+      chosen += __builtin_popcount(word);
+    }
+    if (p->single && chosen != 1) return fail(EG_ERR_BAD_ARG, "a single-choice ballot selects exactly one option");
+  }
+  return EG_OK;
+}
+// the assertions of QuadraticVotingBallot::new (quadratic_voting.rs:240-253)
+static int check_votes(const eg_qv_params* p, size_t n, const uint32_t* votes) {
+  const uint64_t max_vote = eghost::isqrt(p->credits);
+  for (size_t i = 0; i < n; ++i) {
+    uint64_t credit = 0;
+    for (int k = 0; k < p->n_options; ++k) {
+      const uint64_t v = votes[i * (size_t)p->n_options + k];
+      if (v > max_vote) return fail(EG_ERR_BAD_ARG, "a vote exceeds isqrt(credits)");
+      credit += v * v;
+    }
+    if (credit > p->credits) return fail(EG_ERR_BAD_ARG, "votes exceed the credit amount");
+  }
+  return EG_OK;
+}
 static int choice_encrypt_device(eg_choice_params* p, uint64_t base_seed, size_t first, size_t n, int n_selected,
                                  const void* d_selection, uint64_t rng_skip, void* d_out, hipStream_t s) {
   Engine* e = p->eng;
@@ -3787,16 +3821,7 @@ int eg_choice_encrypt_selected_batch(eg_choice_params* p, uint64_t base_seed, si
   Engine* e = p->eng;
   HIPCHK(hipSetDevice(e->ctx->device));
   const size_t sw = ((size_t)p->n_options + 31) / 32;
-  for (size_t i = 0; i < n; ++i) {      // what EncryptedChoice::single / ::new would refuse or mis-prove
-    int chosen = 0;
-    for (size_t w = 0; w < sw; ++w) {
-      const uint32_t word = selection[i * sw + w];
-      const int valid_bits = (int)std::min<size_t>(32, (size_t)p->n_options - 32 * w);
-      if (valid_bits < 32 && (word >> valid_bits)) return fail(EG_ERR_BAD_ARG, "selection has bits beyond the options");
-      chosen += __builtin_popcount(word);
-    }
-    if (p->single && chosen != 1) return fail(EG_ERR_BAD_ARG, "a single-choice ballot selects exactly one option");
-  }
+  TRY(check_selection(p, n, selection));
   DevBuf d, sel;
   TRY(d.alloc(n * e->plan.stride)); TRY(sel.alloc(n * sw * 4));
   TRY(sel.put(selection, n * sw * 4, e->ctx->stream));
@@ -3845,16 +3870,7 @@ int eg_qv_encrypt_votes_batch(eg_qv_params* p, uint64_t base_seed, size_t first,
   if (!p || (n && (!out || !votes))) return fail(EG_ERR_BAD_ARG, "bad argument");
   Engine* e = p->eng;
   HIPCHK(hipSetDevice(e->ctx->device));
-  const uint64_t max_vote = eghost::isqrt(p->credits);
-  for (size_t i = 0; i < n; ++i) {      // the assertions of QuadraticVotingBallot::new (quadratic_voting.rs:240-253)
-    uint64_t credit = 0;
-    for (int k = 0; k < p->n_options; ++k) {
-      const uint64_t v = votes[i * (size_t)p->n_options + k];
-      if (v > max_vote) return fail(EG_ERR_BAD_ARG, "a vote exceeds isqrt(credits)");
-      credit += v * v;
-    }
-    if (credit > p->credits) return fail(EG_ERR_BAD_ARG, "votes exceed the credit amount");
-  }
+  TRY(check_votes(p, n, votes));
   DevBuf d, vv;
   TRY(d.alloc(n * e->plan.stride)); TRY(vv.alloc(n * (size_t)p->n_options * 4));
   TRY(vv.put(votes, n * (size_t)p->n_options * 4, e->ctx->stream));
@@ -3862,6 +3878,170 @@ int eg_qv_encrypt_votes_batch(eg_qv_params* p, uint64_t base_seed, size_t first,
   TRY(d.get(out, n * e->plan.stride, e->ctx->stream));
   HIPCHK(hipStreamSynchronize(e->ctx->stream));
   return EG_OK;
+}
+
+// ---- ballot audits (Benaloh challenge): opened ballots against their ciphertexts (open_kernels.cuh), and the opener of synthetic ballots ----
+// Stateless like weeding: the plan's immutable data (stride, tally items) and the narrow comb tables of G and K only - no lock, no
+// workspace, no running tally, any stream.
+static uint32_t open_slots(const Engine* e) { return (uint32_t)(e->plan.tally_slots.size() / 2); }
+static size_t open_check_scratch_bytes(const Engine* e, size_t n) {
+  if (!e || !e->weed_keys_ok || n >= ego::N_LIMIT || ego::refuse_items(n, open_slots(e))) return 0;
+  return ego::layout(n, open_slots(e)).total;
+}
+// the argument rules, in the order the header gives them; nothing of the params object is looked at before they hold
+static int open_check_args(const Engine* e, size_t n, const ego::Have& h) {
+  const char* why = ego::refuse(n, h);
+  if (why) return fail(EG_ERR_BAD_ARG, std::string("open check: ") + why);
+  if (!e) return fail(EG_ERR_BAD_ARG, "open check: null params");
+  if (!e->weed_keys_ok) return fail(EG_ERR_BAD_ARG, "open check: internal: the tally ciphertexts of this plan are not contiguous wire items");
+  if ((why = ego::refuse_items(n, open_slots(e)))) return fail(EG_ERR_BAD_ARG, std::string("open check: ") + why);
+  return EG_OK;
+}
+static int open_check_launch(Engine* e, size_t n, const void* d_ballots, const void* d_status_in, const void* d_values, const void* d_rand,
+                             void* d_status_out, void* d_found, void* d_scratch, hipStream_t s) {
+  if (const char* why = ego::refuse(n, ego::Have{d_ballots != nullptr, d_values != nullptr, d_rand != nullptr, d_status_out != nullptr, d_found != nullptr}))
+    return fail(EG_ERR_BAD_ARG, std::string("open check: ") + why);
+  if (const char* why = ego::refuse_alignment((uintptr_t)d_ballots | (uintptr_t)d_scratch, (uintptr_t)d_values,
+                                              (uintptr_t)d_rand | (uintptr_t)d_status_in | (uintptr_t)d_status_out | (uintptr_t)d_found))
+    return fail(EG_ERR_BAD_ARG, std::string("open check: ") + why);
+  TRY_(open_check_args(e, n, ego::Have{true, true, true, true, true}));
+  const u32 n_slots = open_slots(e);
+  const ego::Layout L = ego::layout(n, n_slots);
+  if (L.total && !d_scratch) return fail(EG_ERR_BAD_ARG, "open check: null scratch (eg_*_open_check_scratch_bytes says how much)");
+  if (!d_found) return EG_OK;                                            // n == 0 and nowhere to write anything to
+  HIPCHK(hipSetDevice(e->ctx->device));
+  u32* found = static_cast<u32*>(d_found);
+  HIPCHK(hipMemsetAsync(found, 0, 2 * sizeof(u32), s));
+  if (n) {
+    u32* words = reinterpret_cast<u32*>(static_cast<char*>(d_scratch) + L.words);
+    const u32* status = static_cast<const u32*>(d_status_in);
+    const OpenMemDev mem{static_cast<const uint8_t*>(d_ballots), (const u32*)e->d_tally_items, (u64)e->plan.stride,
+                         static_cast<const unsigned long long*>(d_values), static_cast<const u32*>(d_rand), words};
+    const size_t items = n * (size_t)n_slots;
+    hipLaunchKernelGGL(k_open_check, dim3((unsigned)((items + NT - 1) / NT)), dim3(NT), 0, s, mem, status, (u64)n, n_slots,
+                       (const uint4*)e->ctx->tabG, (const uint4*)e->d_tabK, words);
+    hipLaunchKernelGGL(k_open_resolve, dim3((unsigned)((n + NT - 1) / NT)), dim3(NT), 0, s, mem, status, (u64)n, n_slots,
+                       static_cast<u32*>(d_status_out), found);
+  }
+  HIPCHK(hipGetLastError());
+  return EG_OK;
+}
+static int open_check_host(Engine* e, size_t n, const uint8_t* ballots, const uint32_t* status_in, const uint64_t* values, const uint8_t* rand,
+                           uint32_t* status_out, uint32_t* found) {
+  TRY_(open_check_args(e, n, ego::Have{ballots != nullptr, values != nullptr, rand != nullptr, status_out != nullptr, found != nullptr}));
+  if (found) found[0] = found[1] = 0;
+  if (n == 0) return EG_OK;
+  HIPCHK(hipSetDevice(e->ctx->device));
+  const size_t items = n * (size_t)open_slots(e);
+  HostStage st("open check"); TRY_(st.open());
+  void *db, *dsi = nullptr, *dv, *dr, *dso, *dfound, *scratch;
+  TRY_(st.put(&db, ballots, n * e->plan.stride));
+  if (status_in) TRY_(st.put(&dsi, status_in, n * 4));
+  TRY_(st.put(&dv, values, items * 8));
+  TRY_(st.put(&dr, rand, items * ego::RAND_BYTES));
+  TRY_(st.put(&dso, nullptr, n * 4));
+  TRY_(st.put(&dfound, nullptr, 2 * 4));
+  TRY_(st.put(&scratch, nullptr, open_check_scratch_bytes(e, n)));
+  TRY_(open_check_launch(e, n, db, dsi, dv, dr, dso, dfound, scratch, st.s));
+  TRY_(st.get(status_out, dso, n * 4));
+  TRY_(st.get(found, dfound, 2 * 4));
+  TRY_(st.sync());
+  return EG_OK;
+}
+size_t eg_choice_open_check_scratch_bytes(const eg_choice_params* p, size_t n) { return open_check_scratch_bytes(p ? p->eng : nullptr, n); }
+size_t eg_qv_open_check_scratch_bytes(const eg_qv_params* p, size_t n) { return open_check_scratch_bytes(p ? p->eng : nullptr, n); }
+int eg_choice_open_check_device(eg_choice_params* p, size_t n, const void* d_ballots, const void* d_status_in, const void* d_values,
+                                const void* d_rand, void* d_status_out, void* d_found, void* d_scratch, void* stream) {
+  return open_check_launch(p ? p->eng : nullptr, n, d_ballots, d_status_in, d_values, d_rand, d_status_out, d_found, d_scratch, (hipStream_t)stream);
+}
+int eg_qv_open_check_device(eg_qv_params* p, size_t n, const void* d_ballots, const void* d_status_in, const void* d_values, const void* d_rand,
+                            void* d_status_out, void* d_found, void* d_scratch, void* stream) {
+  return open_check_launch(p ? p->eng : nullptr, n, d_ballots, d_status_in, d_values, d_rand, d_status_out, d_found, d_scratch, (hipStream_t)stream);
+}
+int eg_choice_open_check(eg_choice_params* p, size_t n, const uint8_t* ballots, const uint32_t* status_in, const uint64_t* values,
+                         const uint8_t* rand, uint32_t* status_out, uint32_t* found) {
+  return open_check_host(p ? p->eng : nullptr, n, ballots, status_in, values, rand, status_out, found);
+}
+int eg_qv_open_check(eg_qv_params* p, size_t n, const uint8_t* ballots, const uint32_t* status_in, const uint64_t* values, const uint8_t* rand,
+                     uint32_t* status_out, uint32_t* found) {
+  return open_check_host(p ? p->eng : nullptr, n, ballots, status_in, values, rand, status_out, found);
+}
+
+// The opener (open_gen_kernels.cuh): no lock and no workspace either - it reads the shape of the election and nothing else.
+static int open_batch_args(const Engine* e, size_t n, const void* values_out, const void* rand_out) {
+  if (n >= ego::N_LIMIT) return fail(EG_ERR_BAD_ARG, "open batch: n is 2^31 or more");
+  if (n && (!values_out || !rand_out)) return fail(EG_ERR_BAD_ARG, "open batch: null values_out or rand_out");
+  if (const char* why = ego::refuse_alignment(0, (uintptr_t)values_out, (uintptr_t)rand_out)) return fail(EG_ERR_BAD_ARG, std::string("open batch: ") + why);
+  if (!e) return fail(EG_ERR_BAD_ARG, "open batch: null params");
+  if (const char* why = ego::refuse_items(n, open_slots(e))) return fail(EG_ERR_BAD_ARG, std::string("open batch: ") + why);
+  return EG_OK;
+}
+static int choice_open_device(eg_choice_params* p, uint64_t base_seed, size_t first, size_t n, int n_selected, uint64_t rng_skip,
+                              const void* d_selection, void* d_values_out, void* d_rand_out, hipStream_t s) {
+  TRY_(open_batch_args(p ? p->eng : nullptr, n, d_values_out, d_rand_out));
+  if ((uintptr_t)d_selection & 3u) return fail(EG_ERR_BAD_ARG, "open batch: selection must be 4-byte aligned");
+  if (!d_selection && !p->single && (n_selected < 0 || n_selected > p->n_options)) return fail(EG_ERR_BAD_ARG, "open batch: n_selected out of range");
+  if (n == 0) return EG_OK;
+  Engine* e = p->eng;
+  HIPCHK(hipSetDevice(e->ctx->device));
+  eg_launch_choice_open(grid_for(n, e->ctx->cus * 4), s, base_seed + first, n, p->n_options, p->single, n_selected,
+                        static_cast<const u32*>(d_selection), rng_skip, static_cast<unsigned long long*>(d_values_out), static_cast<u32*>(d_rand_out));
+  HIPCHK(hipGetLastError());
+  return EG_OK;
+}
+static int qv_open_device(eg_qv_params* p, uint64_t base_seed, size_t first, size_t n, uint64_t rng_skip, const void* d_votes, void* d_values_out,
+                          void* d_rand_out, hipStream_t s) {
+  TRY_(open_batch_args(p ? p->eng : nullptr, n, d_values_out, d_rand_out));
+  if ((uintptr_t)d_votes & 3u) return fail(EG_ERR_BAD_ARG, "open batch: votes must be 4-byte aligned");
+  if (n == 0) return EG_OK;
+  Engine* e = p->eng;
+  HIPCHK(hipSetDevice(e->ctx->device));
+  const eghost::RangeDecomposition& vr = p->shape.vote_range;
+  eg_launch_qv_open(grid_for(n, e->ctx->cus * 4), s, base_seed + first, n, p->n_options, p->credits, static_cast<const u32*>(d_votes), rng_skip,
+                    ego::range_draws((u32)vr.rings.size(), vr.rings_size()), static_cast<unsigned long long*>(d_values_out),
+                    static_cast<u32*>(d_rand_out));
+  HIPCHK(hipGetLastError());
+  return EG_OK;
+}
+// host arrays: `choices` = the selection or the votes (null: drawn from the second stream), `per_ballot` words of it a ballot
+static int open_batch_host(const Engine* e, size_t n, const uint32_t* choices, size_t per_ballot, uint64_t* values_out, uint8_t* rand_out,
+                           const std::function<int(void*, void*, void*, hipStream_t)>& launch) {
+  TRY_(open_batch_args(e, n, values_out, rand_out));
+  if (n == 0) return EG_OK;
+  HIPCHK(hipSetDevice(e->ctx->device));
+  const size_t items = n * (size_t)open_slots(e);
+  HostStage st("open batch"); TRY_(st.open());
+  void *dc = nullptr, *dv, *dr;
+  if (choices) TRY_(st.put(&dc, choices, n * per_ballot * 4));
+  TRY_(st.put(&dv, nullptr, items * 8));
+  TRY_(st.put(&dr, nullptr, items * ego::RAND_BYTES));
+  TRY_(launch(dc, dv, dr, st.s));
+  TRY_(st.get(values_out, dv, items * 8));
+  TRY_(st.get(rand_out, dr, items * ego::RAND_BYTES));
+  TRY_(st.sync());
+  return EG_OK;
+}
+int eg_choice_open_batch_device(eg_choice_params* p, uint64_t base_seed, size_t first, size_t n, int n_selected, uint64_t rng_skip,
+                                const void* d_selection, void* d_values_out, void* d_rand_out, void* stream) {
+  return choice_open_device(p, base_seed, first, n, n_selected, rng_skip, d_selection, d_values_out, d_rand_out, (hipStream_t)stream);
+}
+int eg_choice_open_batch(eg_choice_params* p, uint64_t base_seed, size_t first, size_t n, int n_selected, uint64_t rng_skip,
+                         const uint32_t* selection, uint64_t* values_out, uint8_t* rand_out) {
+  TRY_(open_batch_args(p ? p->eng : nullptr, n, values_out, rand_out));
+  if (selection) TRY_(check_selection(p, n, selection));
+  return open_batch_host(p->eng, n, selection, ((size_t)p->n_options + 31) / 32, values_out, rand_out,
+                         [&](void* dc, void* dv, void* dr, hipStream_t s) { return choice_open_device(p, base_seed, first, n, n_selected, rng_skip, dc, dv, dr, s); });
+}
+int eg_qv_open_batch_device(eg_qv_params* p, uint64_t base_seed, size_t first, size_t n, uint64_t rng_skip, const void* d_votes,
+                            void* d_values_out, void* d_rand_out, void* stream) {
+  return qv_open_device(p, base_seed, first, n, rng_skip, d_votes, d_values_out, d_rand_out, (hipStream_t)stream);
+}
+int eg_qv_open_batch(eg_qv_params* p, uint64_t base_seed, size_t first, size_t n, uint64_t rng_skip, const uint32_t* votes,
+                     uint64_t* values_out, uint8_t* rand_out) {
+  TRY_(open_batch_args(p ? p->eng : nullptr, n, values_out, rand_out));
+  if (votes) TRY_(check_votes(p, n, votes));
+  return open_batch_host(p->eng, n, votes, (size_t)p->n_options, values_out, rand_out,
+                         [&](void* dc, void* dv, void* dr, hipStream_t s) { return qv_open_device(p, base_seed, first, n, rng_skip, dc, dv, dr, s); });
 }
 
 // CommitmentEquivalenceProof::new per item (prover_kernels.cuh: k_commit_equiv_prove), over the narrow comb tables of G, K and H

@@ -1,7 +1,7 @@
 // voting.cpp -- the reference's examples/voting.rs on the GPU backend, in C++ on top of the C ABI:
 //   `Args::vote`            (examples/voting.rs:179-213)  ./voting [votes] [options] [seed]
 //   `Args::quadratic_vote`  (examples/voting.rs:219-269)  ./voting --qv [votes] [options] [credits] [seed]
-//   options: --devices N, --json, --precincts P, --weighted, --replays K, --signed K, --revotes K, --receipts K, --heads K
+//   options: --devices N, --json, --precincts P, --weighted, --replays K, --signed K, --revotes K, --receipts K, --heads K, --audits K
 // talliers' key -> voters create ballots from their own choices -> verify every ballot -> homomorphic totals -> decrypt and
 // compare with the EXPECTED totals the voters' choices add up to.  Threshold sharing of the key (examples/voting.rs:105-120) is out
 // of scope; a single key pair stands in for the shared key (tests/test_gpu_parity.py::test_threshold_tally_end_to_end
@@ -33,6 +33,11 @@
 // given before: their heads are re-derived from the node store (heads = eg_merkle_heads), their consistency proofs against the present
 // head are issued and checked (consistency / consistency_check: the board only grew), and one old head with a flipped bit must be
 // refused as the old root's mismatch; one summary line is printed.
+// With --audits K (choice ballots), K extra ballots are CHALLENGED instead of cast (the Benaloh challenge of Helios and ElectionGuard): the
+// voting device opens them - the value and the encryption randomness of every ciphertext -, the audit pass (open_check = eg_*_open_check)
+// re-encrypts and compares, and the one device that encrypted another option than the voter pressed is caught.  Every audited ballot,
+// whatever its verdict, is spoiled: its ciphertexts go onto weeding's board, and a device that casts an opened ballot after all is
+// flagged EG_DUP_PRIOR by the weeding of the cast batch.
 //
 //   g++ -std=c++17 -Iinclude examples/voting.cpp -Lelastic_elgamal_amd -leg_hip -Wl,-rpath,$PWD/elastic_elgamal_amd -o voting
 #include <cstdio>
@@ -158,6 +163,37 @@ static bool replayed_tally(const Context& ctx, const Ristretto& group, const Sca
   for (size_t v = 0; v < votes; ++v) ok = ok && w.dup_of[v] == EG_DUP_NONE;
   ok = tally(ctx, group, sk, kept.totals[0], expected, max_value) && ok;
   printf("the weeded totals %s those without the replays\n", ok ? "equal" : "DIFFER from");
+  return ok;
+}
+
+// --audits: K extra ballots are opened, checked and spoiled instead of cast; the first comes from a device that cheats
+static bool audited_ballots(const ChoiceParams& params, const Bytes& ballots, size_t votes, size_t audits, size_t options, uint64_t seed, Rng& rng) {
+  const size_t size = params.ballot_size(), words = (options + 31) / 32;
+  std::vector<size_t> pressed(audits), encrypted(audits);
+  for (size_t i = 0; i < audits; ++i) encrypted[i] = pressed[i] = (size_t)rng.below(options);
+  encrypted[0] = (pressed[0] + 1) % options;                                     // this device encrypts another option than was pressed
+  const Bytes pile = params.encrypt_single_choices(seed, votes, encrypted);      // the devices commit to their ballots ...
+  std::vector<uint32_t> sel(audits * words, 0u);
+  for (size_t i = 0; i < audits; ++i) sel[i * words + encrypted[i] / 32] |= 1u << (encrypted[i] % 32);
+  Opening opening = params.open_batch(seed, votes, audits, 0, 0, sel);           // ... and open them when challenged (test openings: eg_hip.h)
+  for (size_t k = 0; k < options; ++k) opening.values[k] = k == pressed[0] ? 1u : 0u;   // the cheat claims what the voter pressed
+  const Audited a = params.open_check(pile, opening);
+  printf("%u ballots audited, %u failed\n", a.participated, a.failed);
+  bool ok = a.participated == audits && a.failed == 1 && EG_STATUS_KIND(a.status[0]) == EG_ST_BAD_OPENING;
+  for (size_t i = 0; i < audits; ++i)
+    if (a.status[i])
+      printf("  audited ballot #%zu: ciphertext #%u does not open to the claimed value (check %u)\n", i + 1,
+             EG_OPEN_DETAIL_SLOT(EG_STATUS_DETAIL(a.status[i])) + 1, EG_OPEN_DETAIL_CHECK(EG_STATUS_DETAIL(a.status[i])));
+  const Weeded spoiled = params.weed(pile);                                      // every audited ballot is spoiled, whatever its verdict
+  ok = ok && spoiled.appended.size() == audits * options * 64;
+  Bytes all = ballots;                                                           // a device casts the last opened ballot after all
+  all.insert(all.end(), pile.end() - size, pile.end());
+  const auto verdict = params.verify_batch(all);
+  std::vector<uint32_t> status(votes + 1);
+  for (size_t v = 0; v <= votes; ++v) status[v] = verdict.results[v] ? 1u : 0u;
+  const Weeded w = params.weed(all, status, spoiled.appended, false);
+  ok = ok && status[votes] == 0u && w.dup_of[votes] == EG_DUP_PRIOR && w.dropped() == 1;
+  printf("%s: the opened ballot that was cast again %s\n", ok ? "OK" : "MISMATCH", w.dup_of[votes] == EG_DUP_PRIOR ? "is on the board and dropped" : "WAS NOT FLAGGED");
   return ok;
 }
 
@@ -365,7 +401,7 @@ static bool receipt_check(const Context& ctx, const Bytes& ballots, size_t ballo
 int main(int argc, char** argv) {
   bool qv = false, json = false, weighted = false;
   int devices = 1;
-  long precincts = 0, replays = 0, signed_forgeries = -1, revotes = 0, receipts = -1, heads = -1;
+  long precincts = 0, replays = 0, signed_forgeries = -1, revotes = 0, receipts = -1, heads = -1, audits = 0;
   std::vector<std::string> pos;
   for (int i = 1; i < argc; ++i) {
     if (!strcmp(argv[i], "--qv")) qv = true;
@@ -376,6 +412,7 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "--replays") && i + 1 < argc) replays = atol(argv[++i]);
     else if (!strcmp(argv[i], "--signed") && i + 1 < argc) signed_forgeries = atol(argv[++i]);
     else if (!strcmp(argv[i], "--revotes") && i + 1 < argc) revotes = atol(argv[++i]);
+    else if (!strcmp(argv[i], "--audits") && i + 1 < argc) audits = atol(argv[++i]);
     else if (!strcmp(argv[i], "--receipts") && i + 1 < argc) receipts = atol(argv[++i]);
     else if (!strcmp(argv[i], "--heads") && i + 1 < argc) heads = atol(argv[++i]);
     else pos.push_back(argv[i]);
@@ -391,6 +428,7 @@ int main(int argc, char** argv) {
   if (revotes < 0 || (revotes && (qv || options < 2 || (size_t)revotes * 7 > votes))) {
     printf("--revotes K is shown for choice ballots with two options or more and needs 7 K <= votes\n"); return 2;
   }
+  if (audits < 0 || audits > 1000000 || (audits && (qv || options < 2))) { printf("--audits K is shown for choice ballots with two options or more, K in 0..1000000\n"); return 2; }
   if (receipts < -1 || receipts > 1000000) { printf("--receipts must be in 0..1000000\n"); return 2; }
   if (heads < -1 || heads > 1000000 || (heads >= 0 && receipts < 0)) { printf("--heads must be in 0..1000000 and needs --receipts\n"); return 2; }
   if (precincts < 0 || precincts > (long)EG_TALLY_GROUPS_MAX) { printf("--precincts must be in 0..%u\n", EG_TALLY_GROUPS_MAX); return 2; }
@@ -462,6 +500,7 @@ int main(int argc, char** argv) {
     }
     if (replays) ok = replayed_tally(ctx, group, sk, *params[0], ballots, votes, (size_t)replays, expected, votes) && ok;
     if (revotes) ok = revoted_tally(ctx, group, sk, *params[0], ballots, choices, (size_t)revotes, options, (uint32_t)precincts, weighted, seed) && ok;
+    if (audits) ok = audited_ballots(*params[0], ballots, votes, (size_t)audits, options, seed, rng) && ok;
     if (receipts >= 0) {
       std::vector<uint32_t> status(votes, 0u);
       for (size_t i = 0; i < votes; ++i) status[i] = verdict.results[i] ? 1u : 0u;

@@ -115,8 +115,10 @@ enum {
                                      earlier ballot; written by eg_*_weed* into status_out only, detail 0 */
   EG_ST_BAD_SIGNATURE = 15,       /* no verdict of the reference: the voter's Ed25519 signature over the item does not hold; written by
                                      eg_ed25519_verify* only, detail = which check failed (EG_ED25519_*) */
-  EG_ST_SUPERSEDED = 16           /* no verdict of the reference: not the one ballot of its voter that counts; written by eg_roll_* into
+  EG_ST_SUPERSEDED = 16,          /* no verdict of the reference: not the one ballot of its voter that counts; written by eg_roll_* into
                                      status_out only, detail = why (EG_ROLL_SUPERSEDED / _OFF_ROLL / _NOT_CAST) */
+  EG_ST_BAD_OPENING = 17          /* no verdict of the reference: an opened (audited) ballot does not encrypt what its opening says;
+                                     written by eg_*_open_check* only, detail = EG_OPEN_DETAIL(slot, check) */
 };
 #define EG_STATUS_KIND(s) ((s) & 0xffu)
 #define EG_STATUS_DETAIL(s) ((s) >> 8)
@@ -489,6 +491,58 @@ int eg_qv_weed_device(eg_qv_params*, size_t n, const void* d_ballots, const void
 int eg_qv_weed(eg_qv_params*, size_t n, const uint8_t* ballots, const uint32_t* status /* or NULL */, size_t n_prior,
                const uint8_t* board, uint32_t* dup_of, uint32_t* status_out /* or NULL */,
                uint8_t* appended /* or NULL; room for n * n_options * 64 */, size_t* n_appended);
+
+/* ---- ballot audits (the Benaloh challenge): opened ballots re-encrypted and compared in one pass ---------------------------------------
+ * The reference's proofs show that a ballot encrypts SOME admissible value.  A voting device that encrypts option 2 when the voter pressed
+ * option 4 passes every stage of the chain.  Helios, and with guardians in place of the device ElectionGuard, let the voter CHALLENGE the
+ * device before casting: it opens the ballot it has just committed to - reveals the value and the encryption randomness of every
+ * ciphertext -, anyone re-encrypts and compares, and the opened ballot is SPOILED, never counted.  Boards publish these openings in bulk;
+ * these entries re-check a pile of them.
+ * INPUTS.  A ballot's SLOTS are its tally ciphertexts in tally order, exactly the keys of weeding: n_options of them (for quadratic voting
+ * the vote ciphertexts; partial ciphertexts and the credit ciphertext are not opened).  An OPENING of ballot b is, per slot t, a value
+ * values[b n_slots + t] (uint64) and the 32 bytes rand[(b n_slots + t) 32 ..] of a scalar r, little-endian.  Ballot b PARTICIPATES iff
+ * status_in[b] == EG_ST_OK (status_in NULL: every ballot).  The bytes of other ballots and of their openings are never read, and their
+ * status word is handed on.
+ * THE RULE.  For a participating ballot, in slot order and within a slot in this order:
+ *   EG_OPEN_BAD_SCALAR 1  r is not a canonical scalar, r >= l.  ([r + l]G and [r]G have the same encoding: without this check an opening
+ *                         could be published in two forms.)
+ *   EG_OPEN_R          2  the canonical Ristretto encoding of [r]G is not the 32 wire bytes R of the slot
+ *   EG_OPEN_B          3  the encoding of [v]G + [r]K is not the wire bytes B
+ * The comparison is byte equality.  Nothing of the ballot is decoded, so a non-canonical or invalid wire encoding is simply a mismatch.
+ * The FIRST failure wins: status_out[b] = EG_ST_BAD_OPENING | EG_OPEN_DETAIL(slot, check) << 8, and EG_ST_OK otherwise.  status_out may be
+ * status_in itself.  The library WRITES found[0] = ballots that participated, found[1] = ballots that failed.  The verdict is a pure
+ * function of the inputs.  v is any uint64: the pass says what the ballot opens to, not whether that value is admissible - that is the
+ * verify entry's job.  r = 0 and v = 0 are valid; the identity encodes as 32 zero bytes.
+ * SPOILING.  The randomness of an opened ballot is public, so it must never be counted, whatever its verdict.  The recipe needs no entry
+ * of its own: put the 64-byte keys R || B of every audited ballot onto weeding's board as prior entries (run eg_*_weed over the audited
+ * pile with an append, or copy the keys); a later ballot that re-uses an opened ciphertext is then flagged EG_DUP_PRIOR by eg_*_weed.
+ * examples/voting.cpp --audits does this.
+ *
+ * STATELESS as weeding: the params object's immutable plan and the narrow comb tables of G and K only - no lock, no workspace, no running
+ * tally, no wide tables, any stream, beside a verifying thread.  The `_device` form is asynchronous on `stream`, allocates nothing and
+ * never synchronises; d_scratch holds eg_*_open_check_scratch_bytes(params, n) bytes (0 for arguments that would be refused, and for
+ * n == 0): 4 bytes per (ballot, slot).  The host form is the same on host arrays, synchronous, with its own scratch.
+ * EG_ERR_BAD_ARG before anything is launched: n >= 2^31; a NULL ballots / values / rand / status_out / found with n > 0; ballots or scratch
+ * that are not 16-byte aligned, values not 8-byte aligned, rand, status_in, status_out or found not 4-byte aligned (device form); NULL
+ * params; n x n_slots above EG_OPEN_ITEMS_MAX; a NULL scratch pointer when the size is not 0.  n == 0 is valid: found (where given) is
+ * zero. */
+enum { EG_OPEN_BAD_SCALAR = 1, EG_OPEN_R = 2, EG_OPEN_B = 3 };                  /* the check that failed */
+#define EG_OPEN_DETAIL(slot, check) ((uint32_t)(slot) * 4u + (uint32_t)(check))    /* detail of EG_ST_BAD_OPENING */
+#define EG_OPEN_DETAIL_SLOT(detail) ((detail) >> 2)
+#define EG_OPEN_DETAIL_CHECK(detail) ((detail) & 3u)
+#define EG_OPEN_ITEMS_MAX (1u << 31) /* n * n_slots */
+size_t eg_choice_open_check_scratch_bytes(const eg_choice_params*, size_t n);
+int eg_choice_open_check_device(eg_choice_params*, size_t n, const void* d_ballots, const void* d_status_in /* uint32[n] or NULL */,
+                                const void* d_values /* uint64[n x n_options] */, const void* d_rand /* n x n_options x 32 */,
+                                void* d_status_out /* uint32[n] */, void* d_found /* 2 x uint32 */, void* d_scratch, void* stream);
+int eg_choice_open_check(eg_choice_params*, size_t n, const uint8_t* ballots, const uint32_t* status_in /* or NULL */,
+                         const uint64_t* values, const uint8_t* rand, uint32_t* status_out, uint32_t* found /* 2 */);
+size_t eg_qv_open_check_scratch_bytes(const eg_qv_params*, size_t n);
+int eg_qv_open_check_device(eg_qv_params*, size_t n, const void* d_ballots, const void* d_status_in /* uint32[n] or NULL */,
+                            const void* d_values /* uint64[n x n_options] */, const void* d_rand /* n x n_options x 32 */,
+                            void* d_status_out /* uint32[n] */, void* d_found /* 2 x uint32 */, void* d_scratch, void* stream);
+int eg_qv_open_check(eg_qv_params*, size_t n, const uint8_t* ballots, const uint32_t* status_in /* or NULL */, const uint64_t* values,
+                     const uint8_t* rand, uint32_t* status_out, uint32_t* found /* 2 */);
 
 /* ---- voter signatures: Ed25519 (RFC 8032, pure EdDSA) of a batch checked in one pass ------------------------------------------------
  * The reference's proofs bind nothing of the voter: a fresh, valid ballot cast by someone who is not on the roll, or in another voter's
@@ -892,6 +946,26 @@ int eg_qv_encrypt_votes_batch(eg_qv_params*, uint64_t base_seed, size_t first, s
                               const uint32_t* votes /* n x n_options */, uint8_t* out);
 int eg_qv_encrypt_votes_batch_device(eg_qv_params*, uint64_t base_seed, size_t first, size_t n, uint64_t rng_skip,
                                      const void* d_votes, void* d_out, void* stream);
+
+/* THE OPENER of the synthetic ballots above, VARIABLE TIME like the generators (see TIMING): it makes test and benchmark openings for
+ * eg_*_open_check.  A real voting device opens its ballots on its own CPU, in constant time where its threat model asks for it; this is
+ * not that.  The entries reproduce the values and the encryption randomness of the ballots that the generator entries make from the
+ * SAME arguments: eg_choice_encrypt_selected_batch / eg_qv_encrypt_votes_batch with a selection / votes, eg_choice_encrypt_batch /
+ * eg_qv_encrypt_batch_device (rng_skip 0) with NULL, where the choice or the votes come from the second stream.  No point is multiplied: one
+ * ChaCha block and one reduction mod l per slot, at the position the generator drew it.  Choice: option k's r is draw rng_skip + 2k +
+ * #{j < k : option j not chosen}.  Quadratic voting: vote k's r is draw rng_skip + k D, D = rings + sum of the ring sizes of the vote
+ * range.  values_out: n x n_options uint64 (8-byte aligned), rand_out: n x n_options x 32 bytes (4-byte aligned).  Stateless: no lock, no
+ * workspace.  EG_ERR_BAD_ARG: n >= 2^31, NULL outputs with n > 0, misaligned device pointers, NULL params, n x n_options above
+ * EG_OPEN_ITEMS_MAX, n_selected out of range (multi-choice without a selection); the host forms validate the choices as the generators'
+ * host forms do. */
+int eg_choice_open_batch_device(eg_choice_params*, uint64_t base_seed, size_t first, size_t n, int n_selected, uint64_t rng_skip,
+                                const void* d_selection /* or NULL */, void* d_values_out, void* d_rand_out, void* stream);
+int eg_choice_open_batch(eg_choice_params*, uint64_t base_seed, size_t first, size_t n, int n_selected, uint64_t rng_skip,
+                         const uint32_t* selection /* n x ceil(n_options / 32), or NULL */, uint64_t* values_out, uint8_t* rand_out);
+int eg_qv_open_batch_device(eg_qv_params*, uint64_t base_seed, size_t first, size_t n, uint64_t rng_skip,
+                            const void* d_votes /* or NULL */, void* d_values_out, void* d_rand_out, void* stream);
+int eg_qv_open_batch(eg_qv_params*, uint64_t base_seed, size_t first, size_t n, uint64_t rng_skip,
+                     const uint32_t* votes /* n x n_options, or NULL */, uint64_t* values_out, uint8_t* rand_out);
 
 /* CommitmentEquivalenceProof::new (proofs/commitment.rs:134-181) on a commitment-equivalence params object, VARIABLE TIME like the other
  * generators (see TIMING): test and benchmark inputs only.  Item i encrypts values[i] and commits to it, drawing from

@@ -156,6 +156,19 @@ struct Weeded {
   size_t dropped() const { size_t d = 0; for (uint32_t v : dup_of) d += v != EG_DUP_NONE; return d; }
 };
 
+// Ballot audits (eg_*_open_check; eg_hip.h, "ballot audits" has the rule).  An Opening is what a challenged voting device reveals: per
+// ballot and tally ciphertext the value and the 32 bytes of the encryption randomness.  Audited: status[b] = EG_ST_OK, the caller's word of
+// a ballot that did not participate, or EG_ST_BAD_OPENING with EG_OPEN_DETAIL(slot, check).  An opened ballot must never be counted: weed
+// the audited pile onto the board (weed(..., append = true)), so that a later copy of an opened ciphertext is EG_DUP_PRIOR.
+struct Opening {
+  std::vector<uint64_t> values;     // n x options_count()
+  Bytes rand;                       // n x options_count() x 32
+};
+struct Audited {
+  std::vector<uint32_t> status;
+  uint32_t participated = 0, failed = 0;
+};
+
 // ChoiceParams<G, S> (choice.rs:132-196); S is SingleChoice (sum proof) or MultiChoice
 class ChoiceParams {
  public:
@@ -261,6 +274,38 @@ class ChoiceParams {
                    void* d_scratch, void* d_dup_of, void* d_status_out, void* d_board_count, void* d_found, void* stream = nullptr) const {
     check(eg_choice_weed_device(p_, n, d_ballots, d_status, n_prior, d_board, board_cap, hash_seed, d_scratch, d_dup_of, d_status_out, d_board_count,
           d_found, stream));
+  }
+  // ballot audit: the openings of `packed` re-encrypted and compared; `status` empty = every ballot participates
+  Audited open_check(const Bytes& packed, const Opening& opening, const std::vector<uint32_t>& status = {}) const {
+    const size_t n = packed.size() / ballot_size();
+    if (n * ballot_size() != packed.size() || opening.values.size() != n * n_ || opening.rand.size() != 32 * n * n_ ||
+        (!status.empty() && status.size() != n))
+      throw Error(EG_ERR_BAD_ARG, "packed, opening and status disagree about the number of ballots");
+    Audited a;
+    a.status.resize(n);
+    uint32_t found[2] = {0, 0};
+    check(eg_choice_open_check(p_, n, packed.data(), status.empty() ? nullptr : status.data(), opening.values.data(), opening.rand.data(),
+          a.status.data(), found));
+    a.participated = found[0];
+    a.failed = found[1];
+    return a;
+  }
+  // asynchronous device-pointer form: d_scratch of open_check_scratch_bytes(n) bytes, d_found two uint32 the library writes
+  size_t open_check_scratch_bytes(size_t n) const { return eg_choice_open_check_scratch_bytes(p_, n); }
+  void open_check_device(size_t n, const void* d_ballots, const void* d_status_in, const void* d_values, const void* d_rand, void* d_status_out,
+                         void* d_found, void* d_scratch, void* stream = nullptr) const {
+    check(eg_choice_open_check_device(p_, n, d_ballots, d_status_in, d_values, d_rand, d_status_out, d_found, d_scratch, stream));
+  }
+  // the opener of the synthetic ballots of encrypt_batch (selection empty) or of eg_choice_encrypt_selected_batch: VARIABLE TIME, test and
+  // benchmark openings only (see eg_hip.h)
+  Opening open_batch(uint64_t base_seed, size_t first, size_t n, int n_selected = 0, uint64_t rng_skip = 0,
+                     const std::vector<uint32_t>& selection = {}) const {
+    Opening o;
+    o.values.resize(n * n_);
+    o.rand.resize(32 * n * n_);
+    check(eg_choice_open_batch(p_, base_seed, first, n, n_selected, rng_skip, selection.empty() ? nullptr : selection.data(), o.values.data(),
+          o.rand.data()));
+    return o;
   }
   // EncryptedChoice::new for synthetic voters base_seed + first + i (choice.rs:313-349), packed
   Bytes encrypt_batch(uint64_t base_seed, size_t first, size_t n, int n_selected = 0) const {
@@ -393,6 +438,36 @@ class QuadraticVotingParams {
                    void* d_scratch, void* d_dup_of, void* d_status_out, void* d_board_count, void* d_found, void* stream = nullptr) const {
     check(eg_qv_weed_device(p_, n, d_ballots, d_status, n_prior, d_board, board_cap, hash_seed, d_scratch, d_dup_of, d_status_out, d_board_count,
           d_found, stream));
+  }
+  // ballot audit: the openings of `packed` re-encrypted and compared; `status` empty = every ballot participates
+  Audited open_check(const Bytes& packed, const Opening& opening, const std::vector<uint32_t>& status = {}) const {
+    const size_t n = packed.size() / ballot_size();
+    if (n * ballot_size() != packed.size() || opening.values.size() != n * n_ || opening.rand.size() != 32 * n * n_ ||
+        (!status.empty() && status.size() != n))
+      throw Error(EG_ERR_BAD_ARG, "packed, opening and status disagree about the number of ballots");
+    Audited a;
+    a.status.resize(n);
+    uint32_t found[2] = {0, 0};
+    check(eg_qv_open_check(p_, n, packed.data(), status.empty() ? nullptr : status.data(), opening.values.data(), opening.rand.data(),
+          a.status.data(), found));
+    a.participated = found[0];
+    a.failed = found[1];
+    return a;
+  }
+  // asynchronous device-pointer form: d_scratch of open_check_scratch_bytes(n) bytes, d_found two uint32 the library writes
+  size_t open_check_scratch_bytes(size_t n) const { return eg_qv_open_check_scratch_bytes(p_, n); }
+  void open_check_device(size_t n, const void* d_ballots, const void* d_status_in, const void* d_values, const void* d_rand, void* d_status_out,
+                         void* d_found, void* d_scratch, void* stream = nullptr) const {
+    check(eg_qv_open_check_device(p_, n, d_ballots, d_status_in, d_values, d_rand, d_status_out, d_found, d_scratch, stream));
+  }
+  // the opener of the synthetic ballots of eg_qv_encrypt_batch_device (votes empty) or of encrypt_votes_batch: VARIABLE TIME, test and
+  // benchmark openings only (see eg_hip.h)
+  Opening open_batch(uint64_t base_seed, size_t first, size_t n, uint64_t rng_skip = 0, const std::vector<uint32_t>& votes = {}) const {
+    Opening o;
+    o.values.resize(n * n_);
+    o.rand.resize(32 * n * n_);
+    check(eg_qv_open_batch(p_, base_seed, first, n, rng_skip, votes.empty() ? nullptr : votes.data(), o.values.data(), o.rand.data()));
+    return o;
   }
   // QuadraticVotingBallot::new(&params, votes, rng) for voters base_seed + first + i (quadratic_voting.rs:234-284); votes:
   // options_count() numbers per voter with sum(v^2) <= credits.  VARIABLE TIME in the votes (see eg_hip.h): test / synthetic data only.
