@@ -247,6 +247,8 @@ def _load() -> C.CDLL:
         "eg_merkle_consistency": (C.c_int, [vp, sz, vp, C.c_uint64, cp, cp, vp, vp]),
         "eg_merkle_consistency_check_device": (C.c_int, [vp, sz, vp, vp, vp, sz, vp, C.c_uint64, vp, vp, vp, vp]),
         "eg_merkle_consistency_check": (C.c_int, [vp, sz, vp, cp, cp, sz, vp, C.c_uint64, cp, vp, vp]),
+        "eg_merkle_grow_device": (C.c_int, [vp, C.c_uint64, vp, C.c_uint64, vp, vp, vp, vp]),
+        "eg_merkle_grow": (C.c_int, [vp, C.c_uint64, cp, C.c_uint64, cp, vp, vp]),
         "eg_proof_params_create": (C.c_int, [vp, cp, C.c_int, C.c_uint64, C.POINTER(vp)]),
         "eg_share_params_create": (C.c_int, [vp, cp, C.c_uint64, C.c_uint64, C.c_uint64, cp, C.POINTER(vp)]),
         "eg_proof_params_destroy": (None, [vp]),
@@ -801,7 +803,8 @@ class LeafResult:
 class ReceiptLog:
     """Ballot receipts (include/eg_hip.h, "receipt log" has the rule): a Merkle tree (RFC 6962, H = the first 32 bytes of SHA-512) over
     the posted ballots.  The log is the caller's bytes of 32-byte leaves, normally fed weeding's status_out; `prefix` is the election id.
-    Every tree() is a full rebuild; there is no incremental frontier state."""
+    Every tree() is a full rebuild; there is no incremental frontier state.  grow() builds the store of the grown log out of the store of
+    the last head and hashes only what the append changed."""
 
     BAD_INDEX, BAD_LENGTH, MISMATCH = MERKLE_BAD_INDEX, MERKLE_BAD_LENGTH, MERKLE_MISMATCH
     MISMATCH_OLD = MERKLE_MISMATCH_OLD
@@ -980,6 +983,23 @@ class ReceiptLog:
         _check(_load().eg_merkle_consistency_check_device(self.ctx._h, m, d_old_size or None, d_old_root or None, d_proofs or None, proof_stride,
                                                           d_proof_len or None, n_leaves, d_root or None, d_verdict or None, d_found or None,
                                                           stream or None))
+
+    # ---- grow: the tree of N leaves out of the tree of its first m, hashing only what the append changed
+    def grow(self, old_size: int, nodes_old: bytes, log: bytes):
+        """eg_merkle_grow: (root, node store) over the len(log) / 32 leaves of the log, byte for byte what tree(log) returns, out of the
+        node store of its first old_size leaves.  Only the tiles that hold a changed node are hashed again; nodes_old is left as it is."""
+        n = len(log) // MERKLE_HASH_BYTES
+        root = C.create_string_buffer(MERKLE_HASH_BYTES)
+        size = self.nodes_bytes(n)
+        nodes = C.create_string_buffer(max(size, 1))
+        _check(_load().eg_merkle_grow(self.ctx._h, old_size, nodes_old or None, n, log or None, nodes, root))
+        return root.raw, nodes.raw[:size]
+
+    def grow_device(self, old_size: int, d_nodes_old: int, n_leaves: int, d_log: int, d_nodes: int, d_root: int, stream: int = 0):
+        """Asynchronous device-pointer variant (eg_merkle_grow_device): no allocation, no scratch, no host synchronisation, no lock.  The
+        two stores must not overlap."""
+        _check(_load().eg_merkle_grow_device(self.ctx._h, old_size, d_nodes_old or None, n_leaves, d_log or None, d_nodes or None, d_root or None,
+                                             stream or None))
 
 
 def prepared_point_size() -> int:

@@ -38,6 +38,7 @@
 #include "roll_kernels.cuh"
 #include "merkle_kernels.cuh"
 #include "merkle_audit_kernels.cuh"
+#include "merkle_grow_kernels.cuh"
 #include "open_kernels.cuh"
 
 using namespace eg;
@@ -4875,6 +4876,61 @@ int eg_merkle_consistency_check(eg_ctx* c, size_t m, const uint64_t* old_size, c
   TRY_(eg_merkle_consistency_check_device(c, m, ds, dor, dp, proof_stride, dlen, n_leaves, dr, dv, df, st.s));
   TRY_(st.get(verdict, dv, m * 4));
   TRY_(st.get(found, df, 4 * sizeof(u32)));
+  TRY_(st.sync());
+  return EG_OK;
+}
+
+// ---- receipt log, the grow entry: the node store of N leaves out of that of its first m (merkle_grow_kernels.cuh; the plan:
+// merkle_grow_host.hpp).  One copy launch for the tiles that lie wholly inside the old tree, then the tree's launches from tile0 on ----
+static const AlignedMsgs MERKLE_GROW_ALIGNED{"", "merkle: nodes_old, log, nodes and root must be 4-byte aligned"};
+int eg_merkle_grow_device(eg_ctx* c, uint64_t old_size, const void* d_nodes_old, uint64_t n_leaves, const void* d_log, void* d_nodes, void* d_root,
+                          void* stream) {
+  TRY_(merkle_refuse(egm::refuse_grow(old_size, n_leaves, d_nodes_old, d_log != nullptr, d_nodes, d_root != nullptr)));
+  TRY_(check_aligned(MERKLE_GROW_ALIGNED, 0, (uintptr_t)d_nodes_old | (uintptr_t)d_log | (uintptr_t)d_nodes | (uintptr_t)d_root));
+  TRY_(check_ctx("merkle", c));
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)stream;
+  u32* store = static_cast<u32*>(d_nodes);
+  const egm::GrowPlan P = egm::grow_plan(old_size, n_leaves);
+  if (P.table.total) {
+    const bool wide = (((uintptr_t)d_nodes_old | (uintptr_t)d_nodes) & 15u) == 0;
+    const uint64_t units = P.table.total * (wide ? 2u : 8u);
+    const unsigned blocks = (unsigned)std::min<uint64_t>((units + MERKLE_NT - 1) / MERKLE_NT, MERKLE_GROW_COPY_BLOCKS);
+    hipLaunchKernelGGL(k_merkle_grow_copy, dim3(blocks), dim3(MERKLE_NT), 0, s, MerkleGrowCopyDev{static_cast<const u32*>(d_nodes_old), store},
+                       P.table, units, wide ? 1 : 0);
+  }
+  const u32* cur = n_leaves ? static_cast<const u32*>(d_log) : nullptr;
+  for (int k = 0; k < P.n_launches; ++k) {
+    const egm::GrowLaunch& g = P.launch[k];
+    MerkleTileArgs a;
+    a.in = cur; a.n_in = g.n_in; a.store = store; a.top = nullptr; a.steps = g.steps;
+    for (int j = 0; j < egm::T_LOG; ++j) a.off[j] = g.off[j];
+    if (g.tile0 < g.tiles)
+      hipLaunchKernelGGL(k_merkle_grow_tile<egm::T_LOG>, dim3((unsigned)(g.tiles - g.tile0)), dim3(1 << (egm::T_LOG - 2)), 0, s, (u32)g.tile0, a);
+    cur = store + g.off[g.steps - 1] * egm::HASH_WORDS;
+  }
+  hipLaunchKernelGGL(k_merkle_root, dim3(1), dim3(64), 0, s, cur, static_cast<u32*>(d_root));
+  HIPCHK(hipGetLastError());
+  return EG_OK;
+}
+int eg_merkle_grow(eg_ctx* c, uint64_t old_size, const uint8_t* nodes_old, uint64_t n_leaves, const uint8_t* log, uint8_t* nodes, uint8_t* root) {
+  TRY_(merkle_refuse(egm::refuse_grow(old_size, n_leaves, nodes_old, log != nullptr, nodes, root != nullptr)));
+  TRY_(check_ctx("merkle", c));
+  HIPCHK(hipSetDevice(c->device));
+  HostStage st("merkle"); TRY_(st.open());
+  const size_t old_bytes = eg_merkle_nodes_bytes(old_size), store_bytes = eg_merkle_nodes_bytes(n_leaves);
+  const uint64_t first = (old_size >> egm::T_LOG) << egm::T_LOG;      // the leaves below are never read: they are not sent either
+  void *dl = nullptr, *dno = nullptr, *dn = nullptr, *dr;
+  if (n_leaves) {
+    TRY_(st.put(&dl, nullptr, (size_t)n_leaves * egm::HASH_BYTES));
+    TRY_(h2d(static_cast<char*>(dl) + first * egm::HASH_BYTES, log + first * egm::HASH_BYTES, (size_t)(n_leaves - first) * egm::HASH_BYTES, st.s));
+  }
+  if (old_bytes) TRY_(st.put(&dno, nodes_old, old_bytes));
+  if (store_bytes) TRY_(st.put(&dn, nullptr, store_bytes));
+  TRY_(st.put(&dr, nullptr, egm::HASH_BYTES));
+  TRY_(eg_merkle_grow_device(c, old_size, dno, n_leaves, dl, dn, dr, st.s));
+  TRY_(st.get(root, dr, egm::HASH_BYTES));
+  if (store_bytes) TRY_(st.get(nodes, dn, store_bytes));
   TRY_(st.sync());
   return EG_OK;
 }

@@ -1,7 +1,7 @@
 // voting.cpp -- the reference's examples/voting.rs on the GPU backend, in C++ on top of the C ABI:
 //   `Args::vote`            (examples/voting.rs:179-213)  ./voting [votes] [options] [seed]
 //   `Args::quadratic_vote`  (examples/voting.rs:219-269)  ./voting --qv [votes] [options] [credits] [seed]
-//   options: --devices N, --json, --precincts P, --weighted, --replays K, --signed K, --revotes K, --receipts K, --heads K, --audits K
+//   options: --devices N, --json, --precincts P, --weighted, --replays K, --signed K, --revotes K, --receipts K, --heads K, --grow, --audits K
 // talliers' key -> voters create ballots from their own choices -> verify every ballot -> homomorphic totals -> decrypt and
 // compare with the EXPECTED totals the voters' choices add up to.  Threshold sharing of the key (examples/voting.rs:105-120) is out
 // of scope; a single key pair stands in for the shared key (tests/test_gpu_parity.py::test_threshold_tally_end_to_end
@@ -33,6 +33,9 @@
 // given before: their heads are re-derived from the node store (heads = eg_merkle_heads), their consistency proofs against the present
 // head are issued and checked (consistency / consistency_check: the board only grew), and one old head with a flipped bit must be
 // refused as the old root's mismatch; one summary line is printed.
+// With --grow (only with --receipts), the log is taken as two batches: the tree of the first half of its leaves is built, the tree of the
+// whole log is GROWN out of it (grow = eg_merkle_grow: only what the second batch changed is hashed), and its root and node store must
+// equal those of the rebuild; one summary line is printed.
 // With --audits K (choice ballots), K extra ballots are CHALLENGED instead of cast (the Benaloh challenge of Helios and ElectionGuard): the
 // voting device opens them - the value and the encryption randomness of every ciphertext -, the audit pass (open_check = eg_*_open_check)
 // re-encrypts and compares, and the one device that encrypted another option than the voter pressed is caught.  Every audited ballot,
@@ -354,9 +357,20 @@ static bool heads_check(const ReceiptLog& receipts, const Bytes& log, const Merk
   return proven == k && forged_ok && past.found[0] == 0 && v.found[0] == 0 && v.found[1] == 0 && v.found[2] == 0 && v.found[3] == (bent ? 1u : 0u);
 }
 
+// --grow: the log as two batches: the tree of the whole log grown out of the tree of its first half must be the rebuilt tree
+static bool grow_check(const ReceiptLog& receipts, const Bytes& log, const MerkleTree& tree) {
+  const uint64_t size = log.size() / EG_MERKLE_HASH_BYTES, first = size / 2;
+  const MerkleTree old = receipts.tree(Bytes(log.begin(), log.begin() + first * EG_MERKLE_HASH_BYTES));
+  const MerkleTree grown = receipts.grow(first, old, log);
+  const bool same = grown.root == tree.root && grown.nodes == tree.nodes;
+  printf("grown log: the tree of %llu leaves out of the tree of its first %llu: root and node store %s\n", (unsigned long long)size,
+         (unsigned long long)first, same ? "equal the rebuild" : "DIFFER from the rebuild");
+  return same;
+}
+
 // --receipts: the accepted ballots are posted to the receipt log; K receipts and one forged one are checked against the root
 static bool receipt_check(const Context& ctx, const Bytes& ballots, size_t ballot_size, const std::vector<uint32_t>& status, size_t k, uint64_t seed,
-                          long heads = -1) {
+                          long heads = -1, bool grow = false) {
   const size_t n = status.size();
   const std::string id = "election #" + std::to_string(seed);
   const ReceiptLog receipts{ctx, Bytes(id.begin(), id.end())};
@@ -367,6 +381,7 @@ static bool receipt_check(const Context& ctx, const Bytes& ballots, size_t ballo
   printf("receipt log: %llu leaves, root ", (unsigned long long)size);
   for (uint8_t b : tree.root) printf("%02x", b);
   printf("\n");
+  const bool grown_ok = !grow || grow_check(receipts, log, tree);
   std::vector<uint64_t> index;
   Bytes leaves;
   std::vector<size_t> voter;
@@ -378,7 +393,7 @@ static bool receipt_check(const Context& ctx, const Bytes& ballots, size_t ballo
   }
   if (index.empty()) {
     printf("no accepted ballot to issue a receipt for\n");
-    return pass.found[0] == 0 && (heads < 0 || heads_check(receipts, log, tree, (size_t)heads));
+    return pass.found[0] == 0 && grown_ok && (heads < 0 || heads_check(receipts, log, tree, (size_t)heads));
   }
   index.push_back(index[0]);                                       // the forged receipt: the first one with a flipped bit in its leaf
   leaves.insert(leaves.end(), leaves.begin(), leaves.begin() + EG_MERKLE_HASH_BYTES);
@@ -386,7 +401,7 @@ static bool receipt_check(const Context& ctx, const Bytes& ballots, size_t ballo
   const Receipts issued = receipts.paths(index, log, tree.nodes);
   const size_t stride = (size_t)ReceiptLog::depth(size) * EG_MERKLE_HASH_BYTES;
   const ReceiptVerdicts v = receipts.check(index, leaves, issued.paths, stride, issued.path_len, size, tree.root);
-  bool ok = pass.found[0] == size && pass.found[1] == 0;
+  bool ok = pass.found[0] == size && pass.found[1] == 0 && grown_ok;
   for (size_t j = 0; j + 1 < index.size(); ++j) {
     printf("  receipt of voter #%zu: leaf %llu, %u path entries, %s\n", voter[j] + 1, (unsigned long long)index[j], issued.path_len[j],
            v.verdict[j] == 0 ? "proven" : "NOT proven");
@@ -399,7 +414,7 @@ static bool receipt_check(const Context& ctx, const Bytes& ballots, size_t ballo
 }
 
 int main(int argc, char** argv) {
-  bool qv = false, json = false, weighted = false;
+  bool qv = false, json = false, weighted = false, grow = false;
   int devices = 1;
   long precincts = 0, replays = 0, signed_forgeries = -1, revotes = 0, receipts = -1, heads = -1, audits = 0;
   std::vector<std::string> pos;
@@ -407,6 +422,7 @@ int main(int argc, char** argv) {
     if (!strcmp(argv[i], "--qv")) qv = true;
     else if (!strcmp(argv[i], "--json")) json = true;
     else if (!strcmp(argv[i], "--weighted")) weighted = true;
+    else if (!strcmp(argv[i], "--grow")) grow = true;
     else if (!strcmp(argv[i], "--devices") && i + 1 < argc) devices = atoi(argv[++i]);
     else if (!strcmp(argv[i], "--precincts") && i + 1 < argc) precincts = atol(argv[++i]);
     else if (!strcmp(argv[i], "--replays") && i + 1 < argc) replays = atol(argv[++i]);
@@ -431,6 +447,7 @@ int main(int argc, char** argv) {
   if (audits < 0 || audits > 1000000 || (audits && (qv || options < 2))) { printf("--audits K is shown for choice ballots with two options or more, K in 0..1000000\n"); return 2; }
   if (receipts < -1 || receipts > 1000000) { printf("--receipts must be in 0..1000000\n"); return 2; }
   if (heads < -1 || heads > 1000000 || (heads >= 0 && receipts < 0)) { printf("--heads must be in 0..1000000 and needs --receipts\n"); return 2; }
+  if (grow && receipts < 0) { printf("--grow needs --receipts\n"); return 2; }
   if (precincts < 0 || precincts > (long)EG_TALLY_GROUPS_MAX) { printf("--precincts must be in 0..%u\n", EG_TALLY_GROUPS_MAX); return 2; }
 
   // one context per device slot; slot d uses GPU d when the process sees that many, else GPU 0
@@ -504,7 +521,7 @@ int main(int argc, char** argv) {
     if (receipts >= 0) {
       std::vector<uint32_t> status(votes, 0u);
       for (size_t i = 0; i < votes; ++i) status[i] = verdict.results[i] ? 1u : 0u;
-      ok = receipt_check(ctx, ballots, params[0]->ballot_size(), status, (size_t)receipts, seed, heads) && ok;
+      ok = receipt_check(ctx, ballots, params[0]->ballot_size(), status, (size_t)receipts, seed, heads, grow) && ok;
     }
   } else {
     std::vector<std::unique_ptr<QuadraticVotingParams>> params;
@@ -542,7 +559,7 @@ int main(int argc, char** argv) {
     if (receipts >= 0) {
       std::vector<uint32_t> status(votes, 0u);
       for (size_t i = 0; i < votes; ++i) status[i] = verdict.results[i] ? 1u : 0u;
-      ok = receipt_check(ctx, ballots, params[0]->ballot_size(), status, (size_t)receipts, seed, heads) && ok;
+      ok = receipt_check(ctx, ballots, params[0]->ballot_size(), status, (size_t)receipts, seed, heads, grow) && ok;
     }
   }
   printf("%s: the decrypted totals %s the expected ones\n", ok ? "OK" : "MISMATCH", ok ? "equal" : "differ from");

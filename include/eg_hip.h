@@ -729,7 +729,7 @@ int eg_roll_check(eg_ctx*, size_t n, const uint32_t* key_index, const uint32_t* 
  * (log_cap x 32 bytes) and *log_count (uint64) = n_prior + appended.  If they do not fit log_cap nothing is appended, the count is
  * n_prior and found[1] is set.  The library WRITES found[0] = the number of leaves, found[1] = non-zero if the append did not fit.
  * TREE.  Every call is a FULL REBUILD over the N leaves of the log: root (32 bytes) and, optionally, the node store.  There is no
- * incremental frontier state.  One launch per 10 levels: two launches up to 2^20 leaves, three above.  Without a node store the top
+ * incremental frontier state (eg_merkle_grow, below, builds the next store out of the last one).  One launch per 10 levels: two launches up to 2^20 leaves, three above.  Without a node store the top
  * level of every launch goes through eg_merkle_tree_scratch_bytes(N) bytes of scratch (0 up to 1024 leaves).
  * PATHS.  For m requested leaf indices (uint64), one lane each, out of the log and the node store: paths (m x depth(N) x 32 bytes, the
  * unused tail of a row zeroed) and path_len (uint32[m]); an index >= N gives EG_MERKLE_NO_PATH and a zeroed row.
@@ -834,6 +834,32 @@ int eg_merkle_consistency_check_device(eg_ctx*, size_t m, const void* d_old_size
                                        void* stream);
 int eg_merkle_consistency_check(eg_ctx*, size_t m, const uint64_t* old_size, const uint8_t* old_root, const uint8_t* proofs, size_t proof_stride,
                                 const uint32_t* proof_len, uint64_t n_leaves, const uint8_t* root, uint32_t* verdict, uint32_t* found /* 4 */);
+/* The receipt log, continued: GROW.  A board that publishes a head after every batch would pay eg_merkle_tree's full rebuild per batch,
+ * re-hashing nodes that cannot have changed.  eg_merkle_grow builds the node store and the root of the N-leaf log out of the node store
+ * of its first m leaves (old_size) and hashes only what the append changed.
+ * RESULT: nodes and root are byte for byte what eg_merkle_tree(N, log, root, nodes) writes, in the same layout, so paths, heads,
+ * consistency and the two checks work on the grown store unchanged.
+ * WORK.  Store node (L, j) is unchanged by the append exactly when (j + 1) 2^L <= m, but every level above the first starts at another
+ * offset once N grows.  The launches are the tree's: launch k reduces input level L0 = 10 k in tiles of 1024 input nodes.  Its first
+ * tile0 = (m >> L0) >> 10 tiles lie wholly inside the old tree: their nodes on every level of the launch are COPIED from the old store to
+ * the new offset.  The tiles from tile0 on are reduced as eg_merkle_tree reduces them: O(N - m + 1024 depth(N) / 10) hashes.  m == 0 is
+ * a full build; m == N copies the whole tiles and reduces the ragged last tile of each launch again (nothing at all if N is a power of
+ * 1024); N == 0 gives H(""), N == 1 the leaf; the depth may grow by any amount between m and N.
+ * NEVER READ: leaves of the log below (m >> 10) << 10, and old-store nodes with (j + 1) 2^L > m, the old tree's ragged and promoted
+ * nodes.
+ * OUT OF PLACE: the old store is left untouched and stays a valid store for (m, R_m), so receipts against the old head can be served
+ * while the new store is built.  The byte ranges [nodes_old, + eg_merkle_nodes_bytes(m)) and [nodes, + eg_merkle_nodes_bytes(N)) must
+ * not overlap.
+ * The contract is the one above: variable time on public data; stateless; the `_device` form takes no lock, uses no workspace of the
+ * context, allocates nothing, never synchronises and needs no scratch: one copy launch, then the tile launches and the root on the one
+ * stream.  The host form does the same on host arrays, synchronous; the leaves that are never read are not sent to the device either.
+ * EG_ERR_BAD_ARG before anything is launched, and before the context is looked at: old_size > N; old_size or N >=
+ * EG_MERKLE_LEAVES_MAX; a NULL root; a NULL log with N > 0; NULL nodes with N > 1; NULL nodes_old with old_size > 1; overlapping stores;
+ * in the `_device` form any array not 4-byte aligned. */
+int eg_merkle_grow_device(eg_ctx*, uint64_t old_size, const void* d_nodes_old /* eg_merkle_nodes_bytes(old_size); may be NULL for old_size <= 1 */,
+                          uint64_t n_leaves /* >= old_size */, const void* d_log /* n_leaves x 32 */,
+                          void* d_nodes /* eg_merkle_nodes_bytes(n_leaves); may be NULL for n_leaves <= 1 */, void* d_root /* 32 */, void* stream);
+int eg_merkle_grow(eg_ctx*, uint64_t old_size, const uint8_t* nodes_old, uint64_t n_leaves, const uint8_t* log, uint8_t* nodes, uint8_t* root);
 
 /* ---- batch tier on several GPUs of ONE process (SURVEY.md 8b `device_mask`; the reference's host is one single-threaded process,
  * examples/voting.rs:179-213) -----------------------------------------------------------------------------------------------------

@@ -953,7 +953,8 @@ struct VoterRoll {
 };
 
 // Receipt log: a Merkle tree (RFC 6962, H = the first 32 bytes of SHA-512) over the posted ballots (eg_hip.h, "receipt log" has the rule);
-// fed weeding's status_out.  The log is the caller's vector of 32-byte leaves; every tree() is a full rebuild, there is no frontier state.
+// fed weeding's status_out.  The log is the caller's vector of 32-byte leaves; every tree() is a full rebuild, there is no frontier state;
+// grow() builds the tree of the grown log out of the last one and hashes only what the append changed.
 struct LeafPass {
   std::vector<uint64_t> leaf_index;                           // EG_LEAF_NONE: the ballot does not participate
   Bytes leaves;                                               // n x 32, zeroed rows for ballots that do not participate
@@ -1101,6 +1102,22 @@ struct ReceiptLog {
                                 void* stream = nullptr) const {
     ok(eg_merkle_consistency_check_device(ctx.raw(), m, d_old_size, d_old_root, d_proofs, proof_stride, d_proof_len, n_leaves, d_root, d_verdict,
                                           d_found, stream));
+  }
+  // the tree of `log` out of `old`, the tree of its first old_size leaves (eg_hip.h, "GROW"): byte for byte what tree(log) returns, and
+  // only the tiles that the append changed are hashed again; `old` is left as it is
+  MerkleTree grow(uint64_t old_size, const MerkleTree& old, const Bytes& log) const {
+    const uint64_t n = log.size() / EG_MERKLE_HASH_BYTES;
+    if (old.nodes.size() < nodes_bytes(old_size)) throw Error(EG_ERR_BAD_ARG, "the old node store is smaller than a store of old_size leaves");
+    MerkleTree t;
+    t.root.resize(EG_MERKLE_HASH_BYTES);
+    t.nodes.resize(nodes_bytes(n) ? nodes_bytes(n) : 1);
+    ok(eg_merkle_grow(ctx.raw(), old_size, old_size > 1 ? old.nodes.data() : nullptr, n, log.data(), t.nodes.data(), t.root.data()));
+    t.nodes.resize(nodes_bytes(n));
+    return t;
+  }
+  void grow_device(uint64_t old_size, const void* d_nodes_old, uint64_t n_leaves, const void* d_log, void* d_nodes, void* d_root,
+                   void* stream = nullptr) const {
+    ok(eg_merkle_grow_device(ctx.raw(), old_size, d_nodes_old, n_leaves, d_log, d_nodes, d_root, stream));
   }
 
  private:
