@@ -203,6 +203,13 @@ def _load() -> C.CDLL:
         "eg_qv_weed_scratch_bytes": (sz, [vp, sz, sz]),
         "eg_qv_weed_device": (C.c_int, [vp, sz, vp, vp, sz, vp, sz, C.c_uint64, vp, vp, vp, vp, vp, vp]),
         "eg_qv_weed": (C.c_int, [vp, sz, vp, vp, sz, vp, vp, vp, vp, C.POINTER(sz)]),
+        "eg_weed_index_bytes": (sz, [sz]),
+        "eg_weed_index_build_device": (C.c_int, [vp, sz, vp, sz, C.c_uint64, vp, vp, vp]),
+        "eg_weed_index_find_device": (C.c_int, [vp, sz, vp, sz, vp, sz, vp, C.c_uint64, vp, vp]),
+        "eg_choice_weed_indexed_scratch_bytes": (sz, [vp, sz]),
+        "eg_choice_weed_indexed_device": (C.c_int, [vp, sz, vp, vp, sz, vp, sz, vp, C.c_uint64, C.c_uint64, vp, vp, vp, vp, vp, vp]),
+        "eg_qv_weed_indexed_scratch_bytes": (sz, [vp, sz]),
+        "eg_qv_weed_indexed_device": (C.c_int, [vp, sz, vp, vp, sz, vp, sz, vp, C.c_uint64, C.c_uint64, vp, vp, vp, vp, vp, vp]),
         "eg_choice_open_check_scratch_bytes": (sz, [vp, sz]),
         "eg_choice_open_check_device": (C.c_int, [vp, sz, vp, vp, vp, vp, vp, vp, vp, vp]),
         "eg_choice_open_check": (C.c_int, [vp, sz, vp, vp, vp, vp, vp, vp]),
@@ -469,6 +476,25 @@ class Context:
         """d_out[k] = sum over ranks of d_in[r][k] (32-byte encodings): merge of all-gathered per-GPU tallies.
         d_bad: device uint32 counter (zeroed by the caller) of slots that received an undecodable encoding."""
         _check(_load().eg_points_sum_device(self._h, n_ranks, n_points, d_in, d_out, d_bad or None, stream))
+
+    @staticmethod
+    def weed_index_bytes(board_cap: int) -> int:
+        """Bytes of a board index (include/eg_hip.h, "persistent board index") over a board with room for board_cap ciphertexts; 0 for
+        board_cap >= 2^31."""
+        return int(_load().eg_weed_index_bytes(board_cap))
+
+    def weed_index_build_device(self, n_prior: int, d_board: int, board_cap: int, index_seed: int, d_index: int, d_found: int, stream: int = 0):
+        """eg_weed_index_build_device: clears the index and inserts board entries [0, n_prior); asynchronous on `stream`.  d_found: one
+        uint32 the library writes, non-zero if the index overflowed."""
+        _check(_load().eg_weed_index_build_device(self._h, n_prior, d_board or None, board_cap, index_seed & 0xFFFFFFFFFFFFFFFF, d_index or None,
+                                                  d_found or None, stream or None))
+
+    def weed_index_find_device(self, n_q: int, d_keys: int, n_prior: int, d_board: int, board_cap: int, d_index: int, index_seed: int, d_pos: int,
+                               stream: int = 0):
+        """eg_weed_index_find_device: d_pos[q] (uint32) = the smallest board position that holds the 64 bytes of key q, or DUP_NONE.  The
+        index is only read."""
+        _check(_load().eg_weed_index_find_device(self._h, n_q, d_keys or None, n_prior, d_board or None, board_cap, d_index or None,
+                                                 index_seed & 0xFFFFFFFFFFFFFFFF, d_pos or None, stream or None))
 
     def merlin_challenges(self, proto: bytes, msg_label: bytes, msgs, chal_label: bytes, out_len: int = 64):
         """``Transcript::new(proto); append_message(msg_label, m); challenge_bytes(chal_label, out_len)`` for every message m
@@ -1430,6 +1456,23 @@ class _BatchParams:
         _check(self._fn("weed_device")(self._h, n, d_ballots or None, d_status or None, n_prior, d_board or None, board_cap,
                                         hash_seed & 0xFFFFFFFFFFFFFFFF, d_scratch or None, d_dup_of or None, d_status_out or None,
                                         d_board_count or None, d_found or None, stream or None))
+
+    def weed_indexed_scratch_bytes(self, n: int) -> int:
+        """Device scratch that weed_indexed_device needs for n ballots: a function of n alone, whatever the board's size (0 for arguments
+        it refuses)."""
+        return int(self._fn("weed_indexed_scratch_bytes")(self._h, n))
+
+    def weed_indexed_device(self, n: int, d_ballots: int, d_status: int, n_prior: int, d_board: int, board_cap: int, d_index: int,
+                            index_seed: int, hash_seed: int, d_scratch: int, d_dup_of: int, d_found: int, d_status_out: int = 0,
+                            d_board_count: int = 0, stream: int = 0):
+        """weed_device against a persistent board index (eg_*_weed_indexed_device): the same outputs byte for byte at O(batch) per call.
+        d_index: Context.weed_index_bytes(board_cap) bytes, built by Context.weed_index_build_device over board [0, n_prior) with
+        index_seed and maintained by earlier calls; with d_board_count the appended ciphertexts are added to it, without it is only read.
+        index_seed stays unpublished for the life of the index; hash_seed is fresh per call; d_scratch: weed_indexed_scratch_bytes(n)."""
+        _check(self._fn("weed_indexed_device")(self._h, n, d_ballots or None, d_status or None, n_prior, d_board or None, board_cap,
+                                                d_index or None, index_seed & 0xFFFFFFFFFFFFFFFF, hash_seed & 0xFFFFFFFFFFFFFFFF,
+                                                d_scratch or None, d_dup_of or None, d_status_out or None, d_board_count or None,
+                                                d_found or None, stream or None))
 
     def open_check_scratch_bytes(self, n: int) -> int:
         """Device scratch that open_check_device needs for n opened ballots (0 for arguments it refuses)."""

@@ -34,6 +34,7 @@
 #include "group_tally_kernels.cuh"
 #include "share_combine_kernels.cuh"
 #include "weed_kernels.cuh"
+#include "weed_index_kernels.cuh"
 #include "ed25519_kernels.cuh"
 #include "roll_kernels.cuh"
 #include "merkle_kernels.cuh"
@@ -2442,6 +2443,126 @@ int eg_choice_weed(eg_choice_params* p, size_t n, const uint8_t* ballots, const 
 int eg_qv_weed(eg_qv_params* p, size_t n, const uint8_t* ballots, const uint32_t* status, size_t n_prior, const uint8_t* board, uint32_t* dup_of,
                uint32_t* status_out, uint8_t* appended, size_t* n_appended) {
   return weed_host(p ? p->eng : nullptr, n, ballots, status, n_prior, board, dup_of, status_out, appended, n_appended);
+}
+// ---- weeding against a persistent board index (weed_index_kernels.cuh): the board's table is the caller's, a call costs O(batch) ------------
+// Stateless with respect to the library like weeding itself: the index is the caller's device memory, as the roll and the node store are.
+static int weed_index_check(const char* who, size_t n_prior, size_t board_cap, const void* d_board, const void* d_index) {
+  const char* why = egw::refuse_indexed(0, n_prior, board_cap);
+  if (!why && !d_index) why = "null index";
+  if (!why && !d_board && n_prior) why = "null board with n_prior > 0";
+  if (!why && (((uintptr_t)d_board | (uintptr_t)d_index) & 15u)) why = "index and board must be 16-byte aligned";
+  return why ? fail(EG_ERR_BAD_ARG, std::string(who) + ": " + why) : EG_OK;
+}
+size_t eg_weed_index_bytes(size_t board_cap) { return egw::index_bytes(board_cap); }
+int eg_weed_index_build_device(eg_ctx* c, size_t n_prior, const void* d_board, size_t board_cap, uint64_t index_seed, void* d_index, void* d_found,
+                               void* stream) {
+  TRY_(weed_index_check("weed index build", n_prior, board_cap, d_board, d_index));
+  if (!d_found) return fail(EG_ERR_BAD_ARG, "weed index build: null found");
+  if ((uintptr_t)d_found & 3u) return fail(EG_ERR_BAD_ARG, "weed index build: misaligned device pointer");
+  TRY_(check_ctx("weed index build", c));
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)stream;
+  const uint64_t slots = egw::table_slots(board_cap);
+  HIPCHK(hipMemsetAsync(d_index, 0xff, (size_t)slots * sizeof(u32), s));                  // egw::INDEX_EMPTY
+  HIPCHK(hipMemsetAsync(d_found, 0, sizeof(u32), s));
+  if (n_prior)
+    hipLaunchKernelGGL(k_weed_index_add, dim3(grid_for(n_prior, c->cus * 64)), dim3(WEED_NT), 0, s, static_cast<const uint8_t*>(d_board), (uint64_t)0,
+                       (uint64_t)n_prior, (const unsigned long long*)nullptr, (uint64_t)board_cap, static_cast<unsigned int*>(d_index), slots,
+                       index_seed, static_cast<u32*>(d_found));
+  HIPCHK(hipGetLastError());
+  return EG_OK;
+}
+int eg_weed_index_find_device(eg_ctx* c, size_t n_q, const void* d_keys, size_t n_prior, const void* d_board, size_t board_cap, const void* d_index,
+                              uint64_t index_seed, void* d_pos, void* stream) {
+  if (n_q >= egw::N_LIMIT) return fail(EG_ERR_BAD_ARG, "weed index find: n_q is 2^31 or more");
+  TRY_(weed_index_check("weed index find", n_prior, board_cap, d_board, d_index));
+  if (n_q && !d_keys) return fail(EG_ERR_BAD_ARG, "weed index find: null keys");
+  if (n_q && !d_pos) return fail(EG_ERR_BAD_ARG, "weed index find: null pos");
+  if ((uintptr_t)d_keys & 15u) return fail(EG_ERR_BAD_ARG, "weed index find: keys must be 16-byte aligned");
+  if ((uintptr_t)d_pos & 3u) return fail(EG_ERR_BAD_ARG, "weed index find: misaligned device pointer");
+  TRY_(check_ctx("weed index find", c));
+  if (n_q == 0) return EG_OK;
+  HIPCHK(hipSetDevice(c->device));
+  const WeedFindKeysDev keys{static_cast<const uint8_t*>(d_keys), static_cast<const uint8_t*>(d_board), (uint64_t)n_q, (uint64_t)n_prior};
+  hipLaunchKernelGGL(k_weed_index_find, dim3(grid_for(n_q, c->cus * 64)), dim3(WEED_NT), 0, (hipStream_t)stream, keys,
+                     static_cast<const unsigned int*>(d_index), egw::table_slots(board_cap), index_seed, static_cast<u32*>(d_pos));
+  HIPCHK(hipGetLastError());
+  return EG_OK;
+}
+static size_t weed_indexed_scratch_bytes(const Engine* e, size_t n) {
+  if (!e || !e->weed_keys_ok || n >= egw::N_LIMIT || egw::refuse_indexed_keys(n, weed_keys_per_ballot(e))) return 0;
+  return egw::layout_indexed(n, weed_keys_per_ballot(e)).total;
+}
+static int weed_indexed_launch(Engine* e, size_t n, const void* d_ballots, const void* d_status, size_t n_prior, void* d_board, size_t board_cap,
+                               void* d_index, uint64_t index_seed, uint64_t hash_seed, void* d_scratch, void* d_dup_of, void* d_status_out,
+                               void* d_board_count, void* d_found, hipStream_t s) {
+  if (((uintptr_t)d_ballots | (uintptr_t)d_board | (uintptr_t)d_scratch | (uintptr_t)d_index) & 15u)
+    return fail(EG_ERR_BAD_ARG, "weed: ballots, board, index and scratch must be 16-byte aligned");
+  if (((uintptr_t)d_status | (uintptr_t)d_dup_of | (uintptr_t)d_status_out | (uintptr_t)d_found) & 3u || ((uintptr_t)d_board_count & 7u))
+    return fail(EG_ERR_BAD_ARG, "weed: misaligned device pointer");
+  const char* why = egw::refuse_indexed(n, n_prior, board_cap);
+  if (!why && !d_index) why = "null index";
+  if (!why && !d_board && n_prior) why = "null board with n_prior > 0";
+  if (why) return fail(EG_ERR_BAD_ARG, std::string("weed: ") + why);
+  // the board is outside the key limit here: the stateless rules are asked about the batch alone
+  TRY_(weed_check(e, n, 0, board_cap, d_ballots != nullptr, d_dup_of != nullptr, d_found != nullptr, d_board != nullptr, d_board_count != nullptr));
+  const u32 K = weed_keys_per_ballot(e);
+  const egw::Layout L = egw::layout_indexed(n, K);
+  if (L.total && !d_scratch) return fail(EG_ERR_BAD_ARG, "weed: null scratch (eg_*_weed_indexed_scratch_bytes says how much)");
+  if (!d_found && !d_board_count) return EG_OK;                          // n == 0 and nowhere to write anything to
+  HIPCHK(hipSetDevice(e->ctx->device));
+  char* base = static_cast<char*>(d_scratch);
+  u32* found = static_cast<u32*>(d_found);
+  const u32* status = static_cast<const u32*>(d_status);
+  const WeedKeysDev keys{static_cast<const uint8_t*>(d_ballots), static_cast<const uint8_t*>(d_board), (const u32*)e->d_tally_items,
+                         (uint64_t)e->plan.stride, (uint64_t)n, (uint64_t)n_prior, K};
+  WeedKeysDev batch_keys = keys;
+  batch_keys.n_prior = 0;                                                 // the batch table: lanes and references of the batch alone
+  const int cap = e->ctx->cus * 64;
+  const uint64_t index_slots = egw::table_slots(board_cap);
+  if (found) HIPCHK(hipMemsetAsync(found, 0, 3 * sizeof(u32), s));
+  if (n) {
+    unsigned long long* slots = reinterpret_cast<unsigned long long*>(base + L.table);
+    u32* pos = reinterpret_cast<u32*>(base + L.pos);
+    HIPCHK(hipMemsetAsync(slots, 0xff, (size_t)L.slots * sizeof(uint64_t), s));          // egw::EMPTY
+    hipLaunchKernelGGL(k_weed_insert, dim3(grid_for(n * K, cap)), dim3(WEED_NT), 0, s, batch_keys, status, slots, L.slots, hash_seed, found);
+    hipLaunchKernelGGL(k_weed_lookup_indexed, dim3(blocks_of(n)), dim3(WEED_NT), 0, s, keys, status, static_cast<const unsigned int*>(d_index),
+                       index_slots, index_seed, (const unsigned long long*)slots, L.slots, hash_seed, static_cast<u32*>(d_dup_of),
+                       static_cast<u32*>(d_status_out), pos, found);
+    if (d_board_count) {
+      u32* tiles = reinterpret_cast<u32*>(base + L.tiles);
+      u32* total_word = reinterpret_cast<u32*>(base + L.total_word);
+      hipLaunchKernelGGL(k_weed_scan_tiles, dim3(L.n_tiles), dim3(WEED_NT), 0, s, (const u32*)pos, (u32)n, tiles);
+      hipLaunchKernelGGL(k_weed_scan_tops, dim3(1), dim3(64), 0, s, L.n_tiles, tiles, K, (uint64_t)n_prior, (uint64_t)board_cap, total_word,
+                         static_cast<unsigned long long*>(d_board_count), found);
+      hipLaunchKernelGGL(k_weed_scan_apply, dim3(L.n_tiles), dim3(WEED_NT), 0, s, pos, (u32)n, (const u32*)tiles);
+      hipLaunchKernelGGL(k_weed_copy, dim3(grid_for(n * K * 4, cap)), dim3(WEED_NT), 0, s, keys, (const u32*)pos, (const u32*)total_word,
+                         static_cast<uint8_t*>(d_board), (uint64_t)board_cap);
+      // what has just been appended -> the index; the count is on the device, so the grid is sized by the most that can have been
+      hipLaunchKernelGGL(k_weed_index_add, dim3(grid_for(n * K, cap)), dim3(WEED_NT), 0, s, static_cast<const uint8_t*>(d_board), (uint64_t)n_prior,
+                         (uint64_t)n_prior, static_cast<const unsigned long long*>(d_board_count), (uint64_t)board_cap,
+                         static_cast<unsigned int*>(d_index), index_slots, index_seed, found + 2);
+    }
+  } else if (d_board_count) {                                             // nothing to add: the count is n_prior
+    hipLaunchKernelGGL(k_weed_scan_tops, dim3(1), dim3(64), 0, s, 0u, (u32*)nullptr, K, (uint64_t)n_prior, (uint64_t)board_cap, (u32*)nullptr,
+                       static_cast<unsigned long long*>(d_board_count), found);
+  }
+  HIPCHK(hipGetLastError());
+  return EG_OK;
+}
+size_t eg_choice_weed_indexed_scratch_bytes(const eg_choice_params* p, size_t n) { return weed_indexed_scratch_bytes(p ? p->eng : nullptr, n); }
+size_t eg_qv_weed_indexed_scratch_bytes(const eg_qv_params* p, size_t n) { return weed_indexed_scratch_bytes(p ? p->eng : nullptr, n); }
+int eg_choice_weed_indexed_device(eg_choice_params* p, size_t n, const void* d_ballots, const void* d_status, size_t n_prior, void* d_board,
+                                  size_t board_cap, void* d_index, uint64_t index_seed, uint64_t hash_seed, void* d_scratch, void* d_dup_of,
+                                  void* d_status_out, void* d_board_count, void* d_found, void* stream) {
+  return weed_indexed_launch(p ? p->eng : nullptr, n, d_ballots, d_status, n_prior, d_board, board_cap, d_index, index_seed, hash_seed, d_scratch,
+                             d_dup_of, d_status_out, d_board_count, d_found, (hipStream_t)stream);
+}
+int eg_qv_weed_indexed_device(eg_qv_params* p, size_t n, const void* d_ballots, const void* d_status, size_t n_prior, void* d_board, size_t board_cap,
+                              void* d_index, uint64_t index_seed, uint64_t hash_seed, void* d_scratch, void* d_dup_of, void* d_status_out,
+                              void* d_board_count, void* d_found, void* stream) {
+  return weed_indexed_launch(p ? p->eng : nullptr, n, d_ballots, d_status, n_prior, d_board, board_cap, d_index, index_seed, hash_seed, d_scratch,
+                             d_dup_of, d_status_out, d_board_count, d_found, (hipStream_t)stream);
 }
 // builds the wide comb tables now (synchronously, ~12 GB each for G and K) instead of inside the first large verify call
 static int prepare_wide(Engine* e) {

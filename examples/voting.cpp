@@ -1,7 +1,8 @@
 // voting.cpp -- the reference's examples/voting.rs on the GPU backend, in C++ on top of the C ABI:
 //   `Args::vote`            (examples/voting.rs:179-213)  ./voting [votes] [options] [seed]
 //   `Args::quadratic_vote`  (examples/voting.rs:219-269)  ./voting --qv [votes] [options] [credits] [seed]
-//   options: --devices N, --json, --precincts P, --weighted, --replays K, --signed K, --revotes K, --receipts K, --heads K, --grow, --audits K
+//   options: --devices N, --json, --precincts P, --weighted, --replays K, --signed K, --revotes K, --receipts K, --heads K, --grow, --audits K,
+//            --board-index
 // talliers' key -> voters create ballots from their own choices -> verify every ballot -> homomorphic totals -> decrypt and
 // compare with the EXPECTED totals the voters' choices add up to.  Threshold sharing of the key (examples/voting.rs:105-120) is out
 // of scope; a single key pair stands in for the shared key (tests/test_gpu_parity.py::test_threshold_tally_end_to_end
@@ -17,6 +18,9 @@
 // With --replays K, K extra voters resubmit byte-for-byte copies of earlier ballots.  The reference's proofs bind nothing of the voter, so
 // every copy of an accepted ballot verifies; the flow weeds between verify and tally (weed = eg_*_weed: ballots that repeat a ciphertext
 // are flagged), prints the number dropped, tallies what is left (tally_grouped over the weeded status words) and reaches the same totals.
+// With --board-index (only with --replays) the weeding runs as a board of a long election would run it: the board and its index
+// (BoardIndex = eg_weed_index_*) stay in device memory, the honest voters and the replays are two batches through weed_indexed_device, and
+// the same two lines are printed.
 // With --signed K every voter signs their packed ballot (Ed25519 under the election's prefix) with a key of the voters' roster, and K
 // envelopes are forged: a right signature under another voter's roster index, or a flipped bit.  The signature pass (Ed25519::verify =
 // eg_ed25519_verify_batch) runs before the ballots are verified; its status words are chained with the verifier's, and the K forgeries,
@@ -47,7 +51,10 @@
 #include <cstdlib>
 #include <cstring>
 #include <memory>
+#include <random>
 #include <string>
+
+#include <dlfcn.h>
 
 #include "elastic_elgamal_hip.hpp"
 
@@ -142,10 +149,70 @@ static bool weighted_tally(const Context& ctx, const Ristretto& group, const Sca
   return ok;
 }
 
+// --board-index: the board and its index live in device memory between batches.  The C++ interface takes device pointers and leaves the
+// allocation to the host, so the example asks the HIP runtime that libeg_hip.so has already loaded, by name
+struct DeviceMemory {
+  int (*alloc)(void**, size_t) = (int (*)(void**, size_t))dlsym(RTLD_DEFAULT, "hipMalloc");
+  int (*release)(void*) = (int (*)(void*))dlsym(RTLD_DEFAULT, "hipFree");
+  int (*copy)(void*, const void*, size_t, int) = (int (*)(void*, const void*, size_t, int))dlsym(RTLD_DEFAULT, "hipMemcpy");
+  std::vector<void*> held;
+  ~DeviceMemory() { for (void* p : held) release(p); }
+  void* take(size_t bytes, const void* from = nullptr) {
+    void* p = nullptr;
+    if (!alloc || !release || !copy || alloc(&p, bytes ? bytes : 16) != 0) throw Error(EG_ERR_HIP, "no device memory for the board index");
+    held.push_back(p);
+    if (from && bytes) up(p, from, bytes);
+    return p;
+  }
+  void up(void* to, const void* from, size_t bytes) { if (copy(to, from, bytes, 1) != 0) throw Error(EG_ERR_HIP, "host to device copy"); }
+  void down(void* to, const void* from, size_t bytes) { if (copy(to, from, bytes, 2) != 0) throw Error(EG_ERR_HIP, "device to host copy"); }
+};
+// The batches of a day against one board: each through weed_indexed_device, which reads the index, appends the kept ciphertexts to the
+// board and adds exactly those to the index - O(batch) per call, where weed() re-inserts the whole board.  Here the honest voters are the
+// first batch and the replays the second; every replay is then EG_DUP_PRIOR, a ciphertext that is already on the board
+template <class Params>
+static Weeded weed_with_board_index(const Context& ctx, const Params& params, const Bytes& all, const std::vector<uint32_t>& status, size_t first_batch,
+                                    size_t options) {
+  const size_t size = params.ballot_size(), total = status.size(), board_cap = total * options;
+  std::random_device rd;
+  auto draw = [&] { return ((uint64_t)rd() << 32) ^ (uint64_t)rd(); };
+  const BoardIndex index{ctx, board_cap, draw()};                               // the seed stays unpublished for the life of the index
+  DeviceMemory dev;
+  void* d_ballots = dev.take(all.size(), all.data());
+  void* d_status = dev.take(total * 4, status.data());
+  void* d_board = dev.take(board_cap * 64);
+  void* d_index = dev.take(index.bytes());
+  void* d_dup = dev.take(total * 4);
+  void* d_words = dev.take(32);                                                  // the board count (uint64), then found[3]
+  index.build_device(0, d_board, d_index, static_cast<char*>(d_words) + 8);      // an empty board
+  Weeded w;
+  w.dup_of.resize(total);
+  w.status.resize(total);
+  uint64_t n_prior = 0;
+  for (size_t at = 0; at < total;) {
+    const size_t n = at < first_batch ? first_batch - at : total - at;
+    void* d_scratch = dev.take(params.weed_indexed_scratch_bytes(n));
+    char* status_at = static_cast<char*>(d_status) + 4 * at;
+    params.weed_indexed_device(n, static_cast<char*>(d_ballots) + at * size, status_at, n_prior, d_board, board_cap, d_index, index.index_seed,
+                               draw(), d_scratch, static_cast<char*>(d_dup) + 4 * at, status_at, d_words,
+                               static_cast<char*>(d_words) + 8);
+    struct { uint64_t count; uint32_t found[3], pad[3]; } words;
+    dev.down(&words, d_words, 32);                                               // (hipMemcpy waits for the pass)
+    if (words.found[2]) throw Error(EG_ERR_BAD_ARG, "the board has no room");
+    printf("board index: batch of %zu ballots against a board of %llu ciphertexts, %llu after it\n", n, (unsigned long long)n_prior,
+           (unsigned long long)words.count);
+    n_prior = words.count;
+    at += n;
+  }
+  dev.down(w.dup_of.data(), d_dup, total * 4);
+  dev.down(w.status.data(), d_status, total * 4);
+  return w;
+}
+
 // --replays: K extra voters resubmit copies of earlier ballots; verify, weed, tally what is left - the totals of the honest voters
 template <class Params>
 static bool replayed_tally(const Context& ctx, const Ristretto& group, const Scalar& sk, const Params& params, const Bytes& ballots, size_t votes,
-                           size_t replays, const std::vector<uint64_t>& expected, uint64_t max_value) {
+                           size_t replays, const std::vector<uint64_t>& expected, uint64_t max_value, bool board_index = false) {
   const size_t size = params.ballot_size();
   Bytes all = ballots;
   for (size_t i = 0; i < replays; ++i) {
@@ -157,9 +224,11 @@ static bool replayed_tally(const Context& ctx, const Ristretto& group, const Sca
   std::vector<uint32_t> status(votes + replays);
   size_t copies_accepted = 0;
   for (size_t v = 0; v < votes + replays; ++v) { status[v] = verdict.results[v] ? 1u : 0u; copies_accepted += v >= votes && !status[v]; }
-  const Weeded w = params.weed(all, status);
-  for (size_t v = 0; v < w.dup_of.size(); ++v)
-    if (w.dup_of[v] != EG_DUP_NONE) printf("  voter #%zu dropped: repeats a ciphertext of voter #%u\n", v + 1, w.dup_of[v] + 1);
+  const Weeded w = board_index ? weed_with_board_index(ctx, params, all, status, votes, expected.size()) : params.weed(all, status);
+  for (size_t v = 0; v < w.dup_of.size(); ++v) {
+    if (w.dup_of[v] == EG_DUP_PRIOR) printf("  voter #%zu dropped: repeats a ciphertext that is on the board\n", v + 1);
+    else if (w.dup_of[v] != EG_DUP_NONE) printf("  voter #%zu dropped: repeats a ciphertext of voter #%u\n", v + 1, w.dup_of[v] + 1);
+  }
   printf("weeding dropped %zu ballots\n", w.dropped());
   const GroupedTally kept = params.tally_grouped(all, w.status, std::vector<uint32_t>(votes + replays, 0u), 1);
   bool ok = w.dropped() == copies_accepted && kept.accepted[0] == verdict.accepted() - copies_accepted;
@@ -414,7 +483,7 @@ static bool receipt_check(const Context& ctx, const Bytes& ballots, size_t ballo
 }
 
 int main(int argc, char** argv) {
-  bool qv = false, json = false, weighted = false, grow = false;
+  bool qv = false, json = false, weighted = false, grow = false, board_index = false;
   int devices = 1;
   long precincts = 0, replays = 0, signed_forgeries = -1, revotes = 0, receipts = -1, heads = -1, audits = 0;
   std::vector<std::string> pos;
@@ -423,6 +492,7 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "--json")) json = true;
     else if (!strcmp(argv[i], "--weighted")) weighted = true;
     else if (!strcmp(argv[i], "--grow")) grow = true;
+    else if (!strcmp(argv[i], "--board-index")) board_index = true;
     else if (!strcmp(argv[i], "--devices") && i + 1 < argc) devices = atoi(argv[++i]);
     else if (!strcmp(argv[i], "--precincts") && i + 1 < argc) precincts = atol(argv[++i]);
     else if (!strcmp(argv[i], "--replays") && i + 1 < argc) replays = atol(argv[++i]);
@@ -515,7 +585,7 @@ int main(int argc, char** argv) {
       for (size_t i = 0; i < votes; ++i) one_hot[i * options + choices[i]] = 1u;
       ok = signed_tally(ctx, group, sk, *params[0], ballots, votes, (size_t)signed_forgeries, one_hot, options, votes, seed) && ok;
     }
-    if (replays) ok = replayed_tally(ctx, group, sk, *params[0], ballots, votes, (size_t)replays, expected, votes) && ok;
+    if (replays) ok = replayed_tally(ctx, group, sk, *params[0], ballots, votes, (size_t)replays, expected, votes, board_index) && ok;
     if (revotes) ok = revoted_tally(ctx, group, sk, *params[0], ballots, choices, (size_t)revotes, options, (uint32_t)precincts, weighted, seed) && ok;
     if (audits) ok = audited_ballots(*params[0], ballots, votes, (size_t)audits, options, seed, rng) && ok;
     if (receipts >= 0) {
@@ -554,7 +624,7 @@ int main(int argc, char** argv) {
     ok = verdict.accepted() == votes - (forged < votes ? 1 : 0) && tally(ctx, group, sk, verdict.totals, expected, max_votes);
     if (precincts) ok = precinct_tally(ctx, group, sk, *params[0], ballots, verdict, (uint32_t)precincts, expected_by_precinct, expected, max_votes) && ok;
     if (weighted) ok = weighted_tally(ctx, group, sk, *params[0], ballots, verdict, all, options, params[0]->max_votes()) && ok;
-    if (replays) ok = replayed_tally(ctx, group, sk, *params[0], ballots, votes, (size_t)replays, expected, max_votes) && ok;
+    if (replays) ok = replayed_tally(ctx, group, sk, *params[0], ballots, votes, (size_t)replays, expected, max_votes, board_index) && ok;
     if (signed_forgeries >= 0) ok = signed_tally(ctx, group, sk, *params[0], ballots, votes, (size_t)signed_forgeries, all, options, max_votes, seed) && ok;
     if (receipts >= 0) {
       std::vector<uint32_t> status(votes, 0u);

@@ -492,6 +492,55 @@ int eg_qv_weed(eg_qv_params*, size_t n, const uint8_t* ballots, const uint32_t* 
                const uint8_t* board, uint32_t* dup_of, uint32_t* status_out /* or NULL */,
                uint8_t* appended /* or NULL; room for n * n_options * 64 */, size_t* n_appended);
 
+/* ---- weeding against a persistent board index: the board's table kept between batches ---------------------------------------------------
+ * eg_*_weed_device clears a table for n n_options + n_prior keys and re-inserts the whole board in every call: O(board) time and scratch
+ * per batch.  A board that takes batches all day keeps the table instead.  The BOARD INDEX is the open-addressing table over the board's
+ * ciphertexts, held by the caller in device memory between calls like the roll and the node store: eg_weed_index_bytes(board_cap) bytes,
+ * 4 per slot of a table of the smallest power of two >= 2 board_cap, at least 1024 (0 for board_cap >= 2^31).  A slot holds a board
+ * position (below 2^31) or all ones for empty; equal bytes at two board positions share a slot that holds the smaller position.
+ *   eg_weed_index_build_device   clears the index and inserts board entries [0, n_prior) (n_prior == 0: an empty index): start-up,
+ *                                restoring from an archive, after board_cap has grown, re-seeding.  WRITES found[0] (one uint32) =
+ *                                non-zero if the index overflowed (it cannot with the library's own sizing).
+ *   eg_weed_index_find_device    read-only: pos[q] = the smallest board position that holds the 64 bytes of key q, or EG_DUP_NONE - "is
+ *                                this ciphertext on the board", for a spoil check or a voter.
+ *   eg_*_weed_indexed_device     the arguments of eg_*_weed_device plus d_index and index_seed; hash_seed stays the fresh per-call seed of
+ *                                the table of the batch's own keys.  dup_of, status_out (may alias d_status), found[0..2], *d_board_count
+ *                                and the appended board bytes are BYTE FOR BYTE those of eg_*_weed_device over the same ballots, status
+ *                                words and board, under the rule above.  With an append that fits, the index afterwards covers board
+ *                                [0, *d_board_count).  If the append does not fit, found[2] is set, the count is n_prior and neither the
+ *                                board nor a byte of the index changes.  With d_board_count == NULL the index is only read.  found[2] is
+ *                                also set if the index overflows while adding (it cannot with the library's own sizing: the append check
+ *                                holds the load at or below 0.5); the caller then rebuilds the index.
+ * d_scratch holds eg_*_weed_indexed_scratch_bytes(params, n) bytes, a function of n alone: the table of the batch's n n_options keys (8
+ * bytes per slot) and ~4 bytes per ballot.  The cost of a call is O(batch).
+ * CONTRACT.  The index was built and maintained over exactly board [0, n_prior) with this board_cap and this index_seed.  One writer at a
+ * time per index (build, or an indexed pass with an append); the read-only forms (find, an indexed pass without an append) may run
+ * concurrently with each other.  index_seed stays unpublished for the LIFE OF THE INDEX, not for one call; build with a fresh seed
+ * re-seeds at O(board) whenever the host wishes.  Under a wrong or garbage index the verdicts are undefined, but every probe loop is
+ * bounded by the slot count and no reference at or above n_prior is ever dereferenced.  Nothing is ever removed from an index, and it
+ * does not grow past board_cap: allocate a larger one and build.  Each GPU keeps its own index over its copy of the board.
+ * EG_ERR_BAD_ARG before anything is launched: what eg_*_weed_device refuses; a NULL index; an index, keys, board, ballots or scratch that
+ * are not 16-byte aligned; board_cap >= 2^31; n n_options above EG_WEED_KEYS_MAX (the board no longer counts against that limit); for
+ * find, n_q >= 2^31 and NULL keys or pos with n_q > 0.  There are no host-buffer forms: a host that holds its board in host memory has
+ * eg_*_weed. */
+size_t eg_weed_index_bytes(size_t board_cap);
+int eg_weed_index_build_device(eg_ctx*, size_t n_prior, const void* d_board /* board_cap x 64 */, size_t board_cap, uint64_t index_seed,
+                               void* d_index, void* d_found /* 1 x uint32: overflow */, void* stream);
+int eg_weed_index_find_device(eg_ctx*, size_t n_q, const void* d_keys /* n_q x 64 */, size_t n_prior, const void* d_board, size_t board_cap,
+                              const void* d_index, uint64_t index_seed, void* d_pos /* n_q x uint32 */, void* stream);
+size_t eg_choice_weed_indexed_scratch_bytes(const eg_choice_params*, size_t n);
+int eg_choice_weed_indexed_device(eg_choice_params*, size_t n, const void* d_ballots, const void* d_status /* or NULL */, size_t n_prior,
+                                  void* d_board /* board_cap x 64 */, size_t board_cap, void* d_index, uint64_t index_seed,
+                                  uint64_t hash_seed, void* d_scratch, void* d_dup_of /* n x uint32 */, void* d_status_out /* or NULL */,
+                                  void* d_board_count /* uint64, or NULL: no append, the index is only read */,
+                                  void* d_found /* 3 x uint32 */, void* stream);
+size_t eg_qv_weed_indexed_scratch_bytes(const eg_qv_params*, size_t n);
+int eg_qv_weed_indexed_device(eg_qv_params*, size_t n, const void* d_ballots, const void* d_status /* or NULL */, size_t n_prior,
+                              void* d_board /* board_cap x 64 */, size_t board_cap, void* d_index, uint64_t index_seed, uint64_t hash_seed,
+                              void* d_scratch, void* d_dup_of /* n x uint32 */, void* d_status_out /* or NULL */,
+                              void* d_board_count /* uint64, or NULL: no append, the index is only read */,
+                              void* d_found /* 3 x uint32 */, void* stream);
+
 /* ---- ballot audits (the Benaloh challenge): opened ballots re-encrypted and compared in one pass ---------------------------------------
  * The reference's proofs show that a ballot encrypts SOME admissible value.  A voting device that encrypts option 2 when the voter pressed
  * option 4 passes every stage of the chain.  Helios, and with guardians in place of the device ElectionGuard, let the voter CHALLENGE the

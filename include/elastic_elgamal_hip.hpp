@@ -275,6 +275,15 @@ class ChoiceParams {
     check(eg_choice_weed_device(p_, n, d_ballots, d_status, n_prior, d_board, board_cap, hash_seed, d_scratch, d_dup_of, d_status_out, d_board_count,
           d_found, stream));
   }
+  // the same pass against a persistent board index (BoardIndex below): byte for byte the same outputs at O(batch) per call; d_scratch of
+  // weed_indexed_scratch_bytes(n) bytes, whatever the board's size; with d_board_count the appended ciphertexts are added to the index
+  size_t weed_indexed_scratch_bytes(size_t n) const { return eg_choice_weed_indexed_scratch_bytes(p_, n); }
+  void weed_indexed_device(size_t n, const void* d_ballots, const void* d_status, size_t n_prior, void* d_board, size_t board_cap, void* d_index,
+                           uint64_t index_seed, uint64_t hash_seed, void* d_scratch, void* d_dup_of, void* d_status_out, void* d_board_count,
+                           void* d_found, void* stream = nullptr) const {
+    check(eg_choice_weed_indexed_device(p_, n, d_ballots, d_status, n_prior, d_board, board_cap, d_index, index_seed, hash_seed, d_scratch, d_dup_of,
+          d_status_out, d_board_count, d_found, stream));
+  }
   // ballot audit: the openings of `packed` re-encrypted and compared; `status` empty = every ballot participates
   Audited open_check(const Bytes& packed, const Opening& opening, const std::vector<uint32_t>& status = {}) const {
     const size_t n = packed.size() / ballot_size();
@@ -438,6 +447,15 @@ class QuadraticVotingParams {
                    void* d_scratch, void* d_dup_of, void* d_status_out, void* d_board_count, void* d_found, void* stream = nullptr) const {
     check(eg_qv_weed_device(p_, n, d_ballots, d_status, n_prior, d_board, board_cap, hash_seed, d_scratch, d_dup_of, d_status_out, d_board_count,
           d_found, stream));
+  }
+  // the same pass against a persistent board index (BoardIndex below): byte for byte the same outputs at O(batch) per call; d_scratch of
+  // weed_indexed_scratch_bytes(n) bytes, whatever the board's size; with d_board_count the appended ciphertexts are added to the index
+  size_t weed_indexed_scratch_bytes(size_t n) const { return eg_qv_weed_indexed_scratch_bytes(p_, n); }
+  void weed_indexed_device(size_t n, const void* d_ballots, const void* d_status, size_t n_prior, void* d_board, size_t board_cap, void* d_index,
+                           uint64_t index_seed, uint64_t hash_seed, void* d_scratch, void* d_dup_of, void* d_status_out, void* d_board_count,
+                           void* d_found, void* stream = nullptr) const {
+    check(eg_qv_weed_indexed_device(p_, n, d_ballots, d_status, n_prior, d_board, board_cap, d_index, index_seed, hash_seed, d_scratch, d_dup_of,
+          d_status_out, d_board_count, d_found, stream));
   }
   // ballot audit: the openings of `packed` re-encrypted and compared; `status` empty = every ballot participates
   Audited open_check(const Bytes& packed, const Opening& opening, const std::vector<uint32_t>& status = {}) const {
@@ -950,6 +968,28 @@ struct VoterRoll {
     if (!roster_weights.empty()) v.weights_out.resize(n);
     return v;
   }
+};
+
+// Board index: the open-addressing table over the weeding board's ciphertexts, kept by the caller in device memory between batches
+// (eg_hip.h, "persistent board index" has the contract).  The struct holds what must stay the same for the life of an index - the board's
+// room and the seed, which stays unpublished - and the caller holds the device memory: bytes() of it.
+struct BoardIndex {
+  const Context& ctx;
+  size_t board_cap = 0;
+  uint64_t index_seed = 0;
+  size_t bytes() const { return eg_weed_index_bytes(board_cap); }
+  // clears the index and inserts board entries [0, n_prior); d_found: one uint32 the library writes, non-zero after an overflow
+  void build_device(size_t n_prior, const void* d_board, void* d_index, void* d_found, void* stream = nullptr) const {
+    ok(eg_weed_index_build_device(ctx.raw(), n_prior, d_board, board_cap, index_seed, d_index, d_found, stream));
+  }
+  // d_pos[q] (uint32) = the smallest board position that holds the 64 bytes of key q, or EG_DUP_NONE; the index is only read
+  void find_device(size_t n_q, const void* d_keys, size_t n_prior, const void* d_board, const void* d_index, void* d_pos,
+                   void* stream = nullptr) const {
+    ok(eg_weed_index_find_device(ctx.raw(), n_q, d_keys, n_prior, d_board, board_cap, d_index, index_seed, d_pos, stream));
+  }
+
+ private:
+  static void ok(int rc) { if (rc != EG_OK) throw Error(rc, eg_last_error()); }
 };
 
 // Receipt log: a Merkle tree (RFC 6962, H = the first 32 bytes of SHA-512) over the posted ballots (eg_hip.h, "receipt log" has the rule);
