@@ -256,6 +256,13 @@ def _load() -> C.CDLL:
         "eg_merkle_consistency_check": (C.c_int, [vp, sz, vp, cp, cp, sz, vp, C.c_uint64, cp, vp, vp]),
         "eg_merkle_grow_device": (C.c_int, [vp, C.c_uint64, vp, C.c_uint64, vp, vp, vp, vp]),
         "eg_merkle_grow": (C.c_int, [vp, C.c_uint64, cp, C.c_uint64, cp, vp, vp]),
+        "eg_shuffle_key_bytes": (sz, [C.c_uint64]),
+        "eg_shuffle_proof_bytes": (sz, [C.c_uint64]),
+        "eg_shuffle_key_derive_device": (C.c_int, [vp, cp, sz, C.c_uint64, vp, vp, vp]),
+        "eg_shuffle_key_derive": (C.c_int, [vp, cp, sz, C.c_uint64, vp]),
+        "eg_shuffle_verify_scratch_bytes": (sz, [vp, C.c_uint64]),
+        "eg_shuffle_verify_device": (C.c_int, [vp, C.c_uint64, vp, vp, cp, cp, sz, vp, C.c_uint64, vp, vp, vp, vp, vp, sz, vp]),
+        "eg_shuffle_verify": (C.c_int, [vp, C.c_uint64, cp, cp, cp, cp, sz, cp, C.c_uint64, cp, vp, vp, vp]),
         "eg_proof_params_create": (C.c_int, [vp, cp, C.c_int, C.c_uint64, C.POINTER(vp)]),
         "eg_share_params_create": (C.c_int, [vp, cp, C.c_uint64, C.c_uint64, C.c_uint64, cp, C.POINTER(vp)]),
         "eg_proof_params_destroy": (None, [vp]),
@@ -348,6 +355,10 @@ MERKLE_HASH_BYTES = 32           # include/eg_hip.h: EG_MERKLE_HASH_BYTES
 MERKLE_LEAVES_MAX = 1 << 31      # include/eg_hip.h: EG_MERKLE_LEAVES_MAX
 LEAF_NONE = (1 << 64) - 1        # include/eg_hip.h: EG_LEAF_NONE, the leaf_index of a ballot that does not participate
 MERKLE_NO_PATH = 0xFFFFFFFF      # include/eg_hip.h: EG_MERKLE_NO_PATH, the path_len of an index that is not in the log
+SHUFFLE_BAD_ENCODING, SHUFFLE_T1, SHUFFLE_T2, SHUFFLE_T3, SHUFFLE_T41, SHUFFLE_T42, SHUFFLE_CHAIN = 1, 2, 4, 8, 16, 32, 64   # EG_SHUFFLE_*
+SHUFFLE_ROW_BAD, SHUFFLE_ROW_CHAIN = 1, 2    # include/eg_hip.h: EG_SHUFFLE_ROW_*, the bits of a row's word
+SHUFFLE_ROWS_MAX = 1 << 23       # include/eg_hip.h: EG_SHUFFLE_ROWS_MAX
+SHUFFLE_KEY_TRIES = 4096         # include/eg_hip.h: EG_SHUFFLE_KEY_TRIES
 
 
 def pack_json(text, n_options: int, single: bool | None = None, credits: int | None = None, threads: int = 0, max_objects: int = 0):
@@ -1026,6 +1037,61 @@ class ReceiptLog:
         two stores must not overlap."""
         _check(_load().eg_merkle_grow_device(self.ctx._h, old_size, d_nodes_old or None, n_leaves, d_log or None, d_nodes or None, d_root or None,
                                              stream or None))
+
+
+class ShuffleVerifier:
+    """Checks a mixer's proof of a re-encryption shuffle (include/eg_hip.h, "re-encryption shuffles" has the rule).  The commitment key
+    H_0 .. H_cap is derived from `seed` once and serves every shuffle of at most `cap` rows; `K` is the election key.  verify() takes
+    rows of 64 bytes (R || B) as bytes and returns (verdict mask, rows, found); 0 means accepted."""
+
+    BAD_ENCODING, T1, T2, T3, T41, T42, CHAIN = 1, 2, 4, 8, 16, 32, 64
+    ROW_BAD, ROW_CHAIN = SHUFFLE_ROW_BAD, SHUFFLE_ROW_CHAIN
+    ROWS_MAX, KEY_TRIES = SHUFFLE_ROWS_MAX, SHUFFLE_KEY_TRIES
+
+    def __init__(self, ctx: Context, K: bytes, seed: bytes = b"", cap: int = 0, key: bytes = None):
+        self.ctx, self.K = ctx, bytes(K)
+        self.key = bytes(key) if key is not None else self.derive_key(ctx, seed, cap)
+        self.cap = len(self.key) // 32 - 1
+
+    @staticmethod
+    def key_bytes(cap: int) -> int:
+        return int(_load().eg_shuffle_key_bytes(cap))
+
+    @staticmethod
+    def proof_bytes(n: int) -> int:
+        return int(_load().eg_shuffle_proof_bytes(n))
+
+    @staticmethod
+    def derive_key(ctx: Context, seed: bytes, cap: int) -> bytes:
+        """eg_shuffle_key_derive: the 32 (cap + 1) bytes of H_0 .. H_cap."""
+        out = C.create_string_buffer(max(32 * (cap + 1), 1))
+        _check(_load().eg_shuffle_key_derive(ctx._h, bytes(seed) or None, len(seed), cap, out))
+        return out.raw[: 32 * (cap + 1)]
+
+    def verify_scratch_bytes(self, n: int) -> int:
+        return int(_load().eg_shuffle_verify_scratch_bytes(self.ctx._h, n))
+
+    def verify(self, ins: bytes, outs: bytes, proof: bytes, prefix: bytes = b"", want_rows: bool = True):
+        """eg_shuffle_verify: (verdict, rows or None, found)."""
+        n = len(ins) // 64
+        if len(outs) != 64 * n or len(proof) != 288 + 160 * n:
+            raise EgError(f"a shuffle of {n} rows has {64 * n} output bytes and a proof of {288 + 160 * n} bytes")
+        verdict, found = C.c_uint32(0), (C.c_uint32 * 4)()
+        rows = (C.c_uint32 * max(n, 1))() if want_rows else None
+        _check(_load().eg_shuffle_verify(self.ctx._h, n, ins or None, outs or None, self.K, bytes(prefix) or None, len(prefix), self.key, self.cap,
+                                         proof or None, C.byref(verdict), rows, found))
+        return int(verdict.value), (list(rows[:n]) if want_rows else None), list(found)
+
+    def verify_device(self, n: int, d_in: int, d_out: int, d_key: int, d_proof: int, d_verdict: int, d_found: int, d_scratch: int, scratch_bytes: int,
+                      prefix: bytes = b"", d_rows: int = 0, key_cap: int = None, stream: int = 0):
+        """Asynchronous device-pointer variant (eg_shuffle_verify_device): no allocation, no host synchronisation.  d_key: a device copy of
+        the key (32 (key_cap + 1) bytes); d_verdict: one uint32; d_found: 4 uint32; d_rows: n uint32 or 0."""
+        _check(_load().eg_shuffle_verify_device(self.ctx._h, n, d_in or None, d_out or None, self.K, bytes(prefix) or None, len(prefix), d_key or None,
+                                                self.cap if key_cap is None else key_cap, d_proof or None, d_verdict or None, d_rows or None,
+                                                d_found or None, d_scratch or None, scratch_bytes, stream or None))
+
+    def derive_key_device(self, seed: bytes, cap: int, d_key: int, d_exhausted: int, stream: int = 0):
+        _check(_load().eg_shuffle_key_derive_device(self.ctx._h, bytes(seed) or None, len(seed), cap, d_key or None, d_exhausted or None, stream or None))
 
 
 def prepared_point_size() -> int:

@@ -41,6 +41,7 @@
 #include "merkle_audit_kernels.cuh"
 #include "merkle_grow_kernels.cuh"
 #include "open_kernels.cuh"
+#include "shuffle_kernels.cuh"
 
 using namespace eg;
 
@@ -5052,6 +5053,122 @@ int eg_merkle_grow(eg_ctx* c, uint64_t old_size, const uint8_t* nodes_old, uint6
   TRY_(eg_merkle_grow_device(c, old_size, dno, n_leaves, dl, dn, dr, st.s));
   TRY_(st.get(root, dr, egm::HASH_BYTES));
   if (store_bytes) TRY_(st.get(nodes, dn, store_bytes));
+  TRY_(st.sync());
+  return EG_OK;
+}
+
+// ---- re-encryption shuffles: the verifier of a mixer's proof (shuffle_kernels.cuh; the rule: include/eg_hip.h) ---------------------------
+// Stateless like the receipt log: everything lives in the caller's scratch.  The products go through eg_vartime_multi_mul_batch_device and
+// the two roots through eg_merkle_tree_device, as they are; everything is asynchronous on the caller's stream.
+static int shuffle_refuse(const char* why) { return why ? fail(EG_ERR_BAD_ARG, std::string("shuffle: ") + why) : EG_OK; }
+static egsh::Layout shuffle_layout(const eg_ctx* c, uint64_t n) {
+  return egsh::layout(n, (unsigned)c->cus, egm::tree_layout(n).total, msm_scratch_for(c, egsh::BIG_PRODUCTS, 2 * (size_t)n),
+                      msm_scratch_for(c, egsh::SMALL_PRODUCTS, egsh::SMALL_TERMS));
+}
+size_t eg_shuffle_key_bytes(uint64_t cap) { return egsh::key_bytes(cap); }
+size_t eg_shuffle_proof_bytes(uint64_t n) { return egsh::proof_bytes(n); }
+size_t eg_shuffle_verify_scratch_bytes(const eg_ctx* c, uint64_t n) { return c && n <= egsh::ROWS_MAX ? shuffle_layout(c, n).total : 0; }
+int eg_shuffle_key_derive_device(eg_ctx* c, const uint8_t* seed, size_t seed_len, uint64_t cap, void* d_key, void* d_exhausted, void* stream) {
+  TRY_(shuffle_refuse(egsh::refuse_key(cap, seed != nullptr, seed_len, d_key != nullptr)));
+  if (!d_exhausted) return shuffle_refuse("null exhausted word");
+  if (((uintptr_t)d_key | (uintptr_t)d_exhausted) & 3u) return shuffle_refuse("key and the exhausted word must be 4-byte aligned");
+  TRY_(check_ctx("shuffle", c));
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)stream;
+  ShufKeyArgs a;
+  memset(&a, 0, sizeof a);
+  if (seed_len) memcpy(a.seed, seed, seed_len);
+  a.seed_len = (u32)seed_len; a.cap = cap; a.tries = egsh::KEY_TRIES;
+  HIPCHK(hipMemsetAsync(d_exhausted, 0, sizeof(u32), s));
+  hipLaunchKernelGGL(k_shuffle_key, dim3(blocks_of((size_t)cap + 1)), dim3(NT), 0, s, a, static_cast<u32*>(d_key), static_cast<u32*>(d_exhausted));
+  HIPCHK(hipGetLastError());
+  return EG_OK;
+}
+int eg_shuffle_key_derive(eg_ctx* c, const uint8_t* seed, size_t seed_len, uint64_t cap, uint8_t* key) {
+  TRY_(shuffle_refuse(egsh::refuse_key(cap, seed != nullptr, seed_len, key != nullptr)));
+  TRY_(check_ctx("shuffle", c));
+  HIPCHK(hipSetDevice(c->device));
+  HostStage st("shuffle"); TRY_(st.open());
+  void *dk, *de;
+  TRY_(st.put(&dk, nullptr, egsh::key_bytes(cap)));
+  TRY_(st.put(&de, nullptr, sizeof(u32)));
+  TRY_(eg_shuffle_key_derive_device(c, seed, seed_len, cap, dk, de, st.s));
+  u32 exhausted = 0;
+  TRY_(st.get(key, dk, egsh::key_bytes(cap)));
+  TRY_(st.get(&exhausted, de, sizeof exhausted));
+  TRY_(st.sync());
+  if (exhausted) return shuffle_refuse("a generator found no element within EG_SHUFFLE_KEY_TRIES candidates (its bytes are zero); take another seed");
+  return EG_OK;
+}
+int eg_shuffle_verify_device(eg_ctx* c, uint64_t n, const void* d_in, const void* d_out, const uint8_t* K, const uint8_t* prefix, size_t prefix_len,
+                             const void* d_key, uint64_t key_cap, const void* d_proof, void* d_verdict, void* d_rows, void* d_found, void* d_scratch,
+                             size_t scratch_bytes, void* stream) {
+  TRY_(shuffle_refuse(egsh::refuse_verify(n, key_cap, d_in != nullptr, d_out != nullptr, K != nullptr, prefix != nullptr, prefix_len, d_key != nullptr,
+                                          d_proof != nullptr, d_verdict != nullptr, d_found != nullptr)));
+  if (((uintptr_t)d_in | (uintptr_t)d_out | (uintptr_t)d_key | (uintptr_t)d_proof | (uintptr_t)d_verdict | (uintptr_t)d_rows | (uintptr_t)d_found) & 3u)
+    return shuffle_refuse("in, out, key, proof, verdict, rows and found must be 4-byte aligned");
+  if ((uintptr_t)d_scratch & 15u) return shuffle_refuse("scratch must be 16-byte aligned");
+  TRY_(check_ctx("shuffle", c));
+  const egsh::Layout L = shuffle_layout(c, n);
+  if (n && (!d_scratch || scratch_bytes < L.total)) return shuffle_refuse("scratch is null or too small (eg_shuffle_verify_scratch_bytes says how much)");
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_shuffle_begin, dim3(1), dim3(64), 0, s, static_cast<u32*>(d_found), static_cast<u32*>(d_verdict));
+  if (n == 0) { HIPCHK(hipGetLastError()); return EG_OK; }
+  char* base = static_cast<char*>(d_scratch);
+  auto words = [&](size_t off) { return reinterpret_cast<u32*>(base + off); };
+  ShufDev D;
+  D.n = n; D.in = static_cast<const u32*>(d_in); D.out = static_cast<const u32*>(d_out); D.key = static_cast<const u32*>(d_key);
+  D.proof = static_cast<const u32*>(d_proof);
+  D.prefix = reinterpret_cast<const unsigned char*>(base + L.prefix); D.prefix_len = (u32)prefix_len;
+  D.state = words(L.state); D.leaves = words(L.leaves); D.rowbad = reinterpret_cast<unsigned char*>(base + L.rowbad); D.upart = words(L.upart);
+  D.big_scalars = words(L.big_scalars); D.big_points = words(L.big_points); D.big_r = words(L.big_r);
+  D.small_scalars = words(L.small_scalars); D.small_points = words(L.small_points); D.small_r = words(L.small_r);
+  D.rows = static_cast<u32*>(d_rows); D.found = static_cast<u32*>(d_found);
+  if (prefix_len) HIPCHK(hipMemcpyAsync(base + L.prefix, prefix, prefix_len, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(D.state + SHUF_ST_K, K, 32, hipMemcpyHostToDevice, s));
+  const size_t tree_bytes = egm::tree_layout(n).total;
+  const unsigned rb = egsh::row_blocks(n);
+  hipLaunchKernelGGL(k_shuffle_leaf1, dim3(rb), dim3(NT), 0, s, D);
+  TRY_(eg_merkle_tree_device(c, n, D.leaves, D.state + SHUF_ST_ROOT1, nullptr, base + L.tree, tree_bytes, s));
+  hipLaunchKernelGGL(k_shuffle_seed, dim3(1), dim3(64), 0, s, D);
+  hipLaunchKernelGGL(k_shuffle_leaf2, dim3(rb), dim3(NT), 0, s, D);
+  TRY_(eg_merkle_tree_device(c, n, D.leaves, D.state + SHUF_ST_ROOT2, nullptr, base + L.tree, tree_bytes, s));
+  hipLaunchKernelGGL(k_shuffle_x, dim3(1), dim3(64), 0, s, D);
+  hipLaunchKernelGGL(k_shuffle_scalars, dim3(rb), dim3(NT), 0, s, D);
+  hipLaunchKernelGGL(k_shuffle_fold, dim3(1), dim3(NT), 0, s, D, (u32)rb);
+  hipLaunchKernelGGL(k_shuffle_chain, dim3(L.chain_grid), dim3(NT), 0, s, D, (const uint4*)c->tabG, reinterpret_cast<uint4*>(base + L.tables));
+  HIPCHK(hipGetLastError());
+  const size_t msm_big = msm_scratch_for(c, egsh::BIG_PRODUCTS, 2 * (size_t)n), msm_small = msm_scratch_for(c, egsh::SMALL_PRODUCTS, egsh::SMALL_TERMS);
+  TRY_(eg_vartime_multi_mul_batch_device(c, egsh::BIG_PRODUCTS, 2 * (size_t)n, D.big_scalars, D.big_points, D.big_r, msm_big ? base + L.msm : nullptr,
+                                         base + L.big_out, base + L.big_ok, s));
+  TRY_(eg_vartime_multi_mul_batch_device(c, egsh::SMALL_PRODUCTS, egsh::SMALL_TERMS, D.small_scalars, D.small_points, D.small_r,
+                                         msm_small ? base + L.msm : nullptr, base + L.small_out, base + L.small_ok, s));
+  hipLaunchKernelGGL(k_shuffle_close, dim3(1), dim3(64), 0, s, D, (const u32*)words(L.big_out), (const unsigned char*)(base + L.big_ok),
+                     (const u32*)words(L.small_out), (const unsigned char*)(base + L.small_ok), static_cast<u32*>(d_verdict));
+  HIPCHK(hipGetLastError());
+  return EG_OK;
+}
+int eg_shuffle_verify(eg_ctx* c, uint64_t n, const uint8_t* in, const uint8_t* out, const uint8_t* K, const uint8_t* prefix, size_t prefix_len,
+                      const uint8_t* key, uint64_t key_cap, const uint8_t* proof, uint32_t* verdict, uint32_t* rows, uint32_t* found) {
+  TRY_(shuffle_refuse(egsh::refuse_verify(n, key_cap, in != nullptr, out != nullptr, K != nullptr, prefix != nullptr, prefix_len, key != nullptr,
+                                          proof != nullptr, verdict != nullptr, found != nullptr)));
+  TRY_(check_ctx("shuffle", c));
+  HIPCHK(hipSetDevice(c->device));
+  HostStage st("shuffle"); TRY_(st.open());
+  const size_t need = eg_shuffle_verify_scratch_bytes(c, n);
+  void *di = nullptr, *dout = nullptr, *dk = nullptr, *dp = nullptr, *dv, *dr = nullptr, *df, *scratch = nullptr;
+  if (n) {
+    TRY_(st.put(&di, in, (size_t)n * 64)); TRY_(st.put(&dout, out, (size_t)n * 64));
+    TRY_(st.put(&dk, key, ((size_t)n + 1) * 32));                      // the generators behind H_N are never read
+    TRY_(st.put(&dp, proof, egsh::proof_bytes(n)));
+    if (rows) TRY_(st.put(&dr, nullptr, (size_t)n * 4));
+    TRY_(st.put(&scratch, nullptr, need));
+  }
+  TRY_(st.put(&dv, nullptr, 4)); TRY_(st.put(&df, nullptr, 16));
+  TRY_(eg_shuffle_verify_device(c, n, di, dout, K, prefix, prefix_len, dk, key_cap, dp, dv, dr, df, scratch, need, st.s));
+  TRY_(st.get(verdict, dv, 4)); TRY_(st.get(found, df, 16));
+  if (n && rows) TRY_(st.get(rows, dr, (size_t)n * 4));
   TRY_(st.sync());
   return EG_OK;
 }

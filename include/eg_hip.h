@@ -1193,6 +1193,79 @@ int eg_range_decomposition(uint64_t upper_bound, char* buf, size_t cap);
  * 4 verify_bool, 5 verify_range (upper bound), 6 sum-of-squares proof over n_options values, 7 commitment-equivalence proof */
 int eg_plan_describe(int kind, int n_options, uint64_t credits_or_bound, char* buf, size_t cap);
 
+/* ---- re-encryption shuffles: verifying a mixer's proof (csrc/shuffle_kernels.cuh; no reference analogue) -----------------------------
+ * Ballots that cannot be summed (ranked choice, write-ins) leave through a re-encryption mix-net: every mixer permutes and re-encrypts
+ * the posted ciphertexts and proves it; anyone checks the proofs; the last mixer's outputs are decrypted with
+ * eg_combine_shares_batch.  These entries CHECK such a proof - the Terelius-Wikstrom proof as restated by Haenni, Locher, Koenig and
+ * Dubuis (the CHVote pseudo-code), additively over Ristretto255.  The model tests/shuffle_ref.py holds the same rule and a prover; a
+ * prover entry is not part of the library.
+ * FORMS.  A ciphertext is the 64 bytes R || B with R = [r]G, B = [m]G + [r]K (weeding's board layout), K the election key.  Rows are
+ * zero-based, i = 0 .. N-1.  H32(x) = the first 32 bytes of SHA-512(x); MTH = the receipt log's tree over 32-byte leaves;
+ * wide(x) = SHA-512(x) read as a little-endian integer mod l.  le64 / le32 are little-endian.
+ * COMMITMENT KEY: H_0 .. H_cap, 32 bytes each (eg_shuffle_key_bytes(cap) = 32 (cap + 1)).  H_j = the first 32 bytes, top bit cleared, of
+ *   SHA-512("eg-shuffle-v1/generator" || byte(seed_len) || seed || le64(j) || le32(ctr)) for the smallest ctr >= 0 at which those bytes
+ * decode (the decoder's rule) to an element other than the identity; about one candidate in eight does.  A lane gives up after
+ * EG_SHUFFLE_KEY_TRIES candidates: its 32 bytes are zero, the device form counts such lanes in *d_exhausted (uint32) and the host form
+ * returns EG_ERR_BAD_ARG after writing the key.  A key derived for cap serves every N <= cap.
+ * STATEMENT: in[N], out[N], K, the key and a per-call prefix of 0 .. 255 bytes (election id || mixer number).  PROOF: one blob of
+ * eg_shuffle_proof_bytes(N) = 288 + 160 N bytes: the head t1 || t2 || t3 || t41 || t42 (points) || s1 || s2 || s3 || s4 (scalars), then
+ * five planar arrays of N x 32 bytes: c (permutation commitment), c^ (chain), t^, s^, s'.
+ * CHALLENGES.
+ *   leaf1_i = H32(0x00 || in_i || out_i || c_i || H_(i+1)),  root1 = MTH(leaf1)
+ *   seed1   = SHA-512("eg-shuffle-v1/seed" || byte(prefix_len) || prefix || le64(N) || K || H_0 || root1)       (all 64 bytes are used)
+ *   u_i     = wide("eg-shuffle-v1/u" || seed1 || le64(i)),  u = the product of all u_i mod l
+ *   leaf2_i = H32(0x00 || c^_i || t^_i),  root2 = MTH(leaf2)
+ *   x       = wide("eg-shuffle-v1/c" || seed1 || root2 || t1 || t2 || t3 || t41 || t42)
+ * The commitment key and N are inside the hash on purpose: commitment parameters left out of the Fiat-Shamir input broke a deployed
+ * shuffle verifier in 2019.
+ * EQUATIONS, with c^_(-1) = H_0, (R_i, B_i) = in_i, (R'_i, B'_i) = out_i, sums over all rows:
+ *   T1     t1   = [-x](sum c_i - sum H_(i+1)) + [s1]G
+ *   T2     t2   = [-x](c^_(N-1) - [u]H_0) + [s2]G
+ *   T3     t3   = [-x] sum [u_i]c_i + [s3]G + sum [s'_i]H_(i+1)
+ *   T41    t41  = [-x] sum [u_i]B_i - [s4]K + sum [s'_i]B'_i
+ *   T42    t42  = [-x] sum [u_i]R_i - [s4]G + sum [s'_i]R'_i
+ *   CHAIN  t^_i = [-x]c^_i + [s^_i]G + [s'_i]c^_(i-1)                                                           (one per row)
+ * Equality is Ristretto equality: the canonical encoding of the right-hand side is compared with the given 32 bytes, as the Ed25519 pass
+ * compares R.  The given side (t1 .. t42, t^_i) is never decoded, so a non-canonical t can never match.
+ * VERDICT: one uint32 bit mask, 0 = accepted; bits, not "first failure", so the word does not depend on lane order.
+ *   EG_SHUFFLE_BAD_ENCODING  some in, out, c, c^, H_0 .. H_N or K does not decode, or some scalar (s1 .. s4, s^_i, s'_i) is >= l.
+ *                            Every other bit is then 0: products over undecodable inputs mean nothing.
+ *   EG_SHUFFLE_T1 .. _T42    that equation fails
+ *   EG_SHUFFLE_CHAIN         at least one row fails CHAIN
+ * rows (optional uint32[N]): per row EG_SHUFFLE_ROW_BAD if in_i, out_i, c_i or c^_i does not decode or s^_i or s'_i is >= l;
+ * EG_SHUFFLE_ROW_CHAIN if the row's CHAIN fails.  CHAIN of row i is evaluated only where c^_i and c^_(i-1) decode and s^_i, s'_i are
+ * canonical (otherwise the bit is 0), whatever the verdict says.  found (uint32[4]): the rows with ROW_BAD, the rows with ROW_CHAIN, the
+ * smallest index of each (0xffffffff for none).
+ * STATELESS like the receipt log: the `_device` forms are asynchronous on `stream`, allocate nothing and never synchronise; K, prefix
+ * and seed are HOST memory and are copied during the call.  The two roots come from eg_merkle_tree_device and the five sums from
+ * eg_vartime_multi_mul_batch_device (which takes the context's lock for its launches): four products of 2N terms in one call, T2 and
+ * [-s4]K in a second.  d_scratch holds eg_shuffle_verify_scratch_bytes(ctx, N) bytes, the product entry's own scratch included (545
+ * bytes a row, 2304 bytes of tables for each lane of the chain kernel's grid - at most 1024 lanes a compute unit, 604 MB on 256 of them
+ * whatever N - and, from 2N = 2^20 terms on, the bucket method's ~250 bytes a term).  The host forms do the same on
+ * host arrays, synchronous, with their own staging.
+ * EG_ERR_BAD_ARG before anything is launched: N or key_cap above EG_SHUFFLE_ROWS_MAX (2N terms must fit the product entry); N > key_cap;
+ * prefix_len or seed_len > 255 or a NULL prefix / seed with a length; NULL verdict or found; with N > 0 a NULL in, out, K, key or proof;
+ * arrays not 4-byte aligned; a scratch that is NULL, too small or not 16-byte aligned.  The argument rules come before the context is
+ * looked at.  N == 0 is EG_OK with verdict 0 and found = {0, 0, 0xffffffff, 0xffffffff}.  TIMING: variable time; a proof is public. */
+enum { EG_SHUFFLE_BAD_ENCODING = 1, EG_SHUFFLE_T1 = 2, EG_SHUFFLE_T2 = 4, EG_SHUFFLE_T3 = 8, EG_SHUFFLE_T41 = 16, EG_SHUFFLE_T42 = 32,
+       EG_SHUFFLE_CHAIN = 64 };
+enum { EG_SHUFFLE_ROW_BAD = 1, EG_SHUFFLE_ROW_CHAIN = 2 };
+#define EG_SHUFFLE_ROWS_MAX (1u << 23)
+#define EG_SHUFFLE_KEY_TRIES 4096
+size_t eg_shuffle_key_bytes(uint64_t cap);                     /* 0 for cap > EG_SHUFFLE_ROWS_MAX */
+size_t eg_shuffle_proof_bytes(uint64_t n);                     /* 0 for n > EG_SHUFFLE_ROWS_MAX */
+int eg_shuffle_key_derive_device(eg_ctx*, const uint8_t* seed /* host */, size_t seed_len, uint64_t cap, void* d_key /* 32 (cap + 1) */,
+                                 void* d_exhausted /* uint32 */, void* stream);
+int eg_shuffle_key_derive(eg_ctx*, const uint8_t* seed, size_t seed_len, uint64_t cap, uint8_t* key /* 32 (cap + 1) */);
+size_t eg_shuffle_verify_scratch_bytes(const eg_ctx*, uint64_t n);
+int eg_shuffle_verify_device(eg_ctx*, uint64_t n, const void* d_in /* n x 64 */, const void* d_out /* n x 64 */, const uint8_t* K /* host, 32 */,
+                             const uint8_t* prefix /* host */, size_t prefix_len, const void* d_key /* 32 (key_cap + 1) */, uint64_t key_cap,
+                             const void* d_proof /* eg_shuffle_proof_bytes(n) */, void* d_verdict /* uint32 */, void* d_rows /* uint32[n] or NULL */,
+                             void* d_found /* 4 x uint32 */, void* d_scratch, size_t scratch_bytes, void* stream);
+int eg_shuffle_verify(eg_ctx*, uint64_t n, const uint8_t* in, const uint8_t* out, const uint8_t* K, const uint8_t* prefix, size_t prefix_len,
+                      const uint8_t* key, uint64_t key_cap, const uint8_t* proof, uint32_t* verdict, uint32_t* rows /* or NULL */,
+                      uint32_t* found /* 4 */);
+
 /* ---- measurement hooks (bench.py) ------------------------------------------------------------------------------------------
  * Average duration in milliseconds of the dominant kernel (k_eq_table<false, T>: the ring equations) over the launches since the last reset,
  * measured with HIP events on the stream the kernel was launched on; launches = number of launches averaged.

@@ -1164,6 +1164,50 @@ struct ReceiptLog {
   static void ok(int rc) { if (rc != EG_OK) throw Error(rc, eg_last_error()); }
 };
 
+// ---- re-encryption shuffles (eg_hip.h, "re-encryption shuffles" has the rule) -------------------------------------------------------
+// Checks a mixer's proof.  The commitment key H_0 .. H_cap is derived once from a seed and serves every shuffle of at most cap rows.
+struct ShuffleVerdict {
+  uint32_t mask = 0;               // EG_SHUFFLE_* bits, 0 = accepted
+  std::vector<uint32_t> rows;      // EG_SHUFFLE_ROW_* bits per row
+  uint32_t found[4] = {0, 0, 0xffffffffu, 0xffffffffu};
+  bool accepted() const { return mask == 0; }
+};
+struct ShuffleVerifier {
+  const Context& ctx;
+  Element K;
+  Bytes key;
+  uint64_t cap;
+  ShuffleVerifier(const Context& c, const Element& election_key, const Bytes& seed, uint64_t cap_) : ctx(c), K(election_key), cap(cap_) {
+    key.resize(eg_shuffle_key_bytes(cap) ? eg_shuffle_key_bytes(cap) : 1);
+    ok(eg_shuffle_key_derive(ctx.raw(), seed.empty() ? nullptr : seed.data(), seed.size(), cap, key.data()));
+  }
+  static size_t key_bytes(uint64_t cap) { return eg_shuffle_key_bytes(cap); }
+  static size_t proof_bytes(uint64_t n) { return eg_shuffle_proof_bytes(n); }
+  size_t verify_scratch_bytes(uint64_t n) const { return eg_shuffle_verify_scratch_bytes(ctx.raw(), n); }
+  // in, out: n rows of 64 bytes (R || B); proof: proof_bytes(n) bytes
+  ShuffleVerdict verify(const Bytes& in, const Bytes& out, const Bytes& proof, const Bytes& prefix = {}) const {
+    const uint64_t n = in.size() / 64;
+    if (out.size() != in.size() || proof.size() != proof_bytes(n)) throw Error(EG_ERR_BAD_ARG, "shuffle: out or proof has the wrong size for these rows");
+    ShuffleVerdict v;
+    v.rows.resize(n ? n : 1);
+    ok(eg_shuffle_verify(ctx.raw(), n, in.data(), out.data(), K.data(), prefix.empty() ? nullptr : prefix.data(), prefix.size(), key.data(), cap,
+                         proof.data(), &v.mask, v.rows.data(), v.found));
+    v.rows.resize(n);
+    return v;
+  }
+  void verify_device(uint64_t n, const void* d_in, const void* d_out, const Bytes& prefix, const void* d_key, uint64_t key_cap, const void* d_proof,
+                     void* d_verdict, void* d_rows, void* d_found, void* d_scratch, size_t scratch_bytes, void* stream = nullptr) const {
+    ok(eg_shuffle_verify_device(ctx.raw(), n, d_in, d_out, K.data(), prefix.empty() ? nullptr : prefix.data(), prefix.size(), d_key, key_cap, d_proof,
+                                d_verdict, d_rows, d_found, d_scratch, scratch_bytes, stream));
+  }
+  void derive_key_device(const Bytes& seed, uint64_t cap_, void* d_key, void* d_exhausted, void* stream = nullptr) const {
+    ok(eg_shuffle_key_derive_device(ctx.raw(), seed.empty() ? nullptr : seed.data(), seed.size(), cap_, d_key, d_exhausted, stream));
+  }
+
+ private:
+  static void ok(int rc) { if (rc != EG_OK) throw Error(rc, eg_last_error()); }
+};
+
 // ---- tally stage (examples/voting.rs:122-177) ------------------------------------------------------------------------------------
 // Params::combine_shares (sharing/mod.rs:302-325): the first `threshold` of the given (participant index, dh element) pairs ->
 // the combined decryption [x]R, or nullopt when there are too few shares.  Verify the shares first (eg_share_params_create).
