@@ -97,7 +97,7 @@ __device__ __forceinline__ void load_wire_item(u32 w[8], const EngineBufs& B, u3
 // (The first layout, [entry][quad][lane], fetched ~5x more lines than it used because lanes with different digits
 // shared 128-B lines: profiles/r01_bench_pmc_counters.txt of the first measurement.)
 struct WsTable {
-  uint4* base;   // ws + global_lane * 80
+  uint4* base;   // the lane's slice: init() for a lane of a full-block grid; k_ballot_small sets the slice of its (ballot, lane) itself
   __device__ __forceinline__ void init(uint4* ws) { base = ws + ((size_t)blockIdx.x * NT + threadIdx.x) * WS_QUADS; }
   __device__ __forceinline__ void store(int e, const ge_cached& c) {
     u32 w[PT_WORDS];
@@ -182,12 +182,14 @@ struct FixedTable {
     for (int i = 0; i < EG_NL; ++i) { c.ypx.v[i] = w[i]; c.ymx.v[i] = w[EG_NL + i]; c.xy2d.v[i] = w[2 * EG_NL + i]; }
   }
 };
-// transcript state: word-interleaved LDS column per lane (positions are wave-uniform => conflict free)
-struct LdsState {
+// transcript state: word-interleaved LDS column per lane, STRIDE columns side by side (positions are wave-uniform => conflict free)
+template <int STRIDE>
+struct LdsStateT {
   u32* base;
-  __device__ __forceinline__ u32 rd(int i) const { return base[i * NT]; }
-  __device__ __forceinline__ void wr(int i, u32 v) { base[i * NT] = v; }
+  __device__ __forceinline__ u32 rd(int i) const { return base[i * STRIDE]; }
+  __device__ __forceinline__ void wr(int i, u32 v) { base[i * STRIDE] = v; }
 };
+using LdsState = LdsStateT<NT>;       // a column per thread of a full block: k_hash, k_encode_hash, the provers
 
 
 }  // namespace eg

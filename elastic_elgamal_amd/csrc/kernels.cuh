@@ -16,6 +16,12 @@
 //   k_hash         LDS + VALU (Keccak-f[1600])
 //   k_encode_hash  k_encode_batch + k_hash of a stage in one launch, two ballots a lane (single choice, up to 7 options)
 //   k_status, k_tally_*   trivial
+//
+// What decides a ballot's verdict is written ONCE, as a __device__ __forceinline__ body per step that takes (B, b, record...): wire_point_decode,
+// wire_scalar_check, point_derive, eq_shared_chains, eq_term_by_term, point_encode_plain, hash_program, ballot_status.  The kernels
+// here wrap a body in their grid-stride loop over (record, ballot); k_ballot_small (latency_kernels.cuh) calls the same bodies from its
+// one workgroup a ballot.  A change to a rule, a code or an order is therefore made in one place for both paths.  (eq_direct is shared
+// by k_eq_direct and k_eq_direct_h alone: k_ballot_small evaluates an equation of that family through eq_term_by_term.)
 #pragma once
 #include <hip/hip_runtime.h>
 #include "device_io.cuh"
@@ -45,57 +51,58 @@ __device__ __forceinline__ void load_scalar(u32 s[8], const EngineBufs& B, u32 b
 }
 
 // ---- k_decode_points: deserialize_element for every wire point (ristretto.rs:93-95) --------------------------------
+// bad_item keeps the smallest code of a malformed item of the ballot, item * 4 + 2 for a point and + 1 for a scalar (ballot_status)
+__device__ __forceinline__ void wire_point_decode(const EngineBufs& B, u32 b, const egplan::WireItem it) {
+  u32 w[8];
+  load_wire_item(w, B, b, it.item);
+  ge p;
+  const bool ok = ristretto_decode(p, w);
+  store_pt(B.pts, B.cap, it.slot, b, p);
+  if (!ok) atomicMin(&B.bad_item[b], (u32)it.item * 4u + 2u);
+}
 // (two waves per SIMD: v_mad_u64_u32 reaches its full issue rate only with a second wave to alternate with, profiles/r01_ubench_valu_rates.txt)
 __global__ void __launch_bounds__(NT, 2) k_decode_points(EngineBufs B, const egplan::WireItem* items, int n_items) {
   const size_t total = (size_t)n_items * B.n;
-  for (size_t j = (size_t)blockIdx.x * NT + threadIdx.x; j < total; j += (size_t)gridDim.x * NT) {
-    const u32 k = (u32)(j / B.n), b = (u32)(j % B.n);
-    const egplan::WireItem it = items[k];
-    u32 w[8];
-    load_wire_item(w, B, b, it.item);
-    ge p;
-    const bool ok = ristretto_decode(p, w);
-    store_pt(B.pts, B.cap, it.slot, b, p);
-    if (!ok) atomicMin(&B.bad_item[b], (u32)it.item * 4u + 2u);
-  }
+  for (size_t j = (size_t)blockIdx.x * NT + threadIdx.x; j < total; j += (size_t)gridDim.x * NT)
+    wire_point_decode(B, (u32)(j % B.n), items[(u32)(j / B.n)]);
 }
 
 // ---- k_check_scalars: deserialize_scalar canonical check (ristretto.rs:59-62) -------------------------------------------
+__device__ __forceinline__ void wire_scalar_check(const EngineBufs& B, u32 b, const egplan::WireItem it) {
+  u32 w[8];
+  load_wire_item(w, B, b, it.item);
+  if (!sc_is_canonical(w)) atomicMin(&B.bad_item[b], (u32)it.item * 4u + 1u);
+}
 __global__ void __launch_bounds__(NT) k_check_scalars(EngineBufs B, const egplan::WireItem* items, int n_items) {
   const size_t total = (size_t)n_items * B.n;
-  for (size_t j = (size_t)blockIdx.x * NT + threadIdx.x; j < total; j += (size_t)gridDim.x * NT) {
-    const u32 k = (u32)(j / B.n), b = (u32)(j % B.n);
-    const egplan::WireItem it = items[k];
-    u32 w[8];
-    load_wire_item(w, B, b, it.item);
-    if (!sc_is_canonical(w)) atomicMin(&B.bad_item[b], (u32)it.item * 4u + 1u);
-  }
+  for (size_t j = (size_t)blockIdx.x * NT + threadIdx.x; j < total; j += (size_t)gridDim.x * NT)
+    wire_scalar_check(B, (u32)(j % B.n), items[(u32)(j / B.n)]);
 }
 
 // ---- k_derive_points: sums / differences of points (choice.rs:363, ring.rs:338, range.rs:564-572) ----------------------------
+__device__ __forceinline__ void point_derive(const EngineBufs& B, u32 b, const egplan::DeriveClass dc, const egplan::DeriveTerm* terms) {
+  ge acc;
+  ge_identity(acc);
+#pragma unroll 1
+  for (u32 t = 0; t < dc.term_count; ++t) {
+    const egplan::DeriveTerm dt = terms[dc.term_first + t];
+    ge p;
+    if (dt.is_const) load_const_pt(p, B.cpts, dt.slot);
+    else load_pt(p, B.pts, B.cap, dt.slot, b);
+    ge_cached pc;
+    ge_to_cached(pc, p);
+    ge_cached_cneg(pc, dt.neg != 0);
+    ge_p1p1 r;
+    ge_add(r, acc, pc);
+    ge_add_to_p3(acc, r);
+  }
+  store_pt(B.pts, B.cap, dc.out_slot, b, acc);
+}
 __global__ void __launch_bounds__(NT) k_derive_points(EngineBufs B, const egplan::DeriveClass* classes,
                                                       const egplan::DeriveTerm* terms, int class_first, int n_classes) {
   const size_t total = (size_t)n_classes * B.n;
-  for (size_t j = (size_t)blockIdx.x * NT + threadIdx.x; j < total; j += (size_t)gridDim.x * NT) {
-    const u32 c = class_first + (u32)(j / B.n), b = (u32)(j % B.n);
-    const egplan::DeriveClass dc = classes[c];
-    ge acc;
-    ge_identity(acc);
-#pragma unroll 1
-    for (u32 t = 0; t < dc.term_count; ++t) {
-      const egplan::DeriveTerm dt = terms[dc.term_first + t];
-      ge p;
-      if (dt.is_const) load_const_pt(p, B.cpts, dt.slot);
-      else load_pt(p, B.pts, B.cap, dt.slot, b);
-      ge_cached pc;
-      ge_to_cached(pc, p);
-      ge_cached_cneg(pc, dt.neg != 0);
-      ge_p1p1 r;
-      ge_add(r, acc, pc);
-      ge_add_to_p3(acc, r);
-    }
-    store_pt(B.pts, B.cap, dc.out_slot, b, acc);
-  }
+  for (size_t j = (size_t)blockIdx.x * NT + threadIdx.x; j < total; j += (size_t)gridDim.x * NT)
+    point_derive(B, (u32)(j % B.n), classes[class_first + (u32)(j / B.n)], terms);
 }
 
 // ---- k_base_tables: comb tables of every ring base (once per base and ballot; shared by all equations of the ring) -----------
@@ -189,10 +196,41 @@ __device__ __forceinline__ void eq_fixed_terms(ge& acc, const EngineBufs& B, u32
   }
 }
 
+// several table-backed bases: groups of up to `group` terms share a doubling chain (Straus).  sign(t, w) is the caller's storage for
+// word w of the sign vector of the group's term t (sc_teeth_signs), a column of LDS: the group size is what fits there.  acc = the sum
+// of the variable-base terms; the caller adds the fixed-base terms and stores.  (The step bodies take their plan record BY VALUE: a
+// reference to a record in global memory would be read again after every store of the body.)
+template <int T, class SignWord>
+__device__ __forceinline__ void eq_shared_chains(ge& acc, const EngineBufs& B, u32 b, const egplan::JobClass jc, const egplan::VarTerm* terms,
+                                                 int group, SignWord sign) {
+  const int nt = (int)jc.term_count;
+#pragma unroll 1
+  for (int t0 = 0; t0 < nt; t0 += group) {
+    const int m = min(group, nt - t0);
+#pragma unroll 1
+    for (int t = 0; t < m; ++t) {
+      u32 s[8], sg[9];
+      load_scalar(s, B, b, terms[jc.term_first + t0 + t].s, true);
+      sc_teeth_signs<T>(sg, s);
+#pragma unroll
+      for (int w = 0; w < 9; ++w) sign(t, w) = sg[w];
+    }
+    ge part;
+    ge_teeth_mul_multi<T>(part, m,
+        [&](int t, int col, int& idx, bool& neg) { sc_teeth_column<T>([&](int w) { return sign(t, w); }, col, idx, neg); },
+        [&](int t, int idx, ge_cached& e) {
+          const BaseTable bt{B.btab + ((size_t)terms[jc.term_first + t0 + t].base * B.cap + b) * btab_quads<T>()};
+          bt.load(e, idx);
+        });
+    if (t0 == 0) acc = part;
+    else { ge sum; ge_add_full(sum, acc, part); acc = sum; }
+  }
+}
+
 template <bool MULTI, int T>
 __global__ void __launch_bounds__(NT, EG_EQ_WAVES) k_eq_table(EngineBufs B, const egplan::JobClass* classes, const egplan::VarTerm* terms,
                                                     int class_first, int n_classes, int group) {
-  extern __shared__ u32 eq_signs[];          // MULTI: [group][9][NT] sign vectors of the multipliers (sc_teeth_signs)
+  extern __shared__ u32 eq_signs[];          // MULTI: [group][9][NT] sign vectors of the multipliers
   const size_t total = (size_t)n_classes * B.n;
   for (size_t j = (size_t)blockIdx.x * NT + threadIdx.x; j < total; j += (size_t)gridDim.x * NT) {
     const u32 c = class_first + (u32)(j / B.n), b = (u32)(j % B.n);
@@ -207,31 +245,7 @@ __global__ void __launch_bounds__(NT, EG_EQ_WAVES) k_eq_table(EngineBufs B, cons
       BaseTable bt{B.btab + ((size_t)vt.base * B.cap + b) * btab_quads<T>()};
       ge_teeth_mul<T>(acc, bt, rows);
     } else {
-      // groups of up to `group` terms share a doubling chain (the group size is what fits LDS at two blocks per CU)
-      const int nt = (int)jc.term_count;
-#pragma unroll 1
-      for (int t0 = 0; t0 < nt; t0 += group) {
-        const int m = min(group, nt - t0);
-#pragma unroll 1
-        for (int t = 0; t < m; ++t) {
-          u32 s[8], sg[9];
-          load_scalar(s, B, b, terms[jc.term_first + t0 + t].s, true);
-          sc_teeth_signs<T>(sg, s);
-#pragma unroll
-          for (int w = 0; w < 9; ++w) eq_signs[(t * 9 + w) * NT + threadIdx.x] = sg[w];
-        }
-        ge part;
-        ge_teeth_mul_multi<T>(part, m,
-            [&](int t, int col, int& idx, bool& neg) {
-              sc_teeth_column<T>([&](int w) { return eq_signs[(t * 9 + w) * NT + threadIdx.x]; }, col, idx, neg);
-            },
-            [&](int t, int idx, ge_cached& e) {
-              const BaseTable bt{B.btab + ((size_t)terms[jc.term_first + t0 + t].base * B.cap + b) * btab_quads<T>()};
-              bt.load(e, idx);
-            });
-        if (t0 == 0) acc = part;
-        else { ge sum; ge_add_full(sum, acc, part); acc = sum; }
-      }
+      eq_shared_chains<T>(acc, B, b, jc, terms, group, [&](int t, int w) -> u32& { return eq_signs[(t * 9 + w) * NT + threadIdx.x]; });
     }
     eq_fixed_terms(acc, B, b, jc);
     store_pt(B.dpt, B.cap, jc.out_slot, b, acc);       // encoded (as 2 * acc) by k_encode_batch
@@ -239,7 +253,19 @@ __global__ void __launch_bounds__(NT, EG_EQ_WAVES) k_eq_table(EngineBufs B, cons
 }
 
 // one base WITHOUT a table (used once: the sum of the ciphertexts in the log-equality proof, log_equality.rs:160-164): uniform signed
-// radix-16 ladder over a per-lane table {1..8}P kept in a workspace slice
+// radix-16 ladder over a per-lane table {1..8}P kept in a workspace slice; acc = the product and the fixed-base terms
+__device__ __forceinline__ void eq_direct(ge& acc, const EngineBufs& B, u32 b, const egplan::JobClass jc, const egplan::VarTerm* terms,
+                                          WsTable& tab) {
+  const egplan::VarTerm vt = terms[jc.term_first];
+  u32 s[8], dg[8];
+  load_scalar(s, B, b, vt.s, true);
+  sc_recode_radix16(dg, s);
+  ge p;
+  load_pt(p, B.pts, B.cap, vt.slot, b);
+  ge_var_table_build(tab, p);
+  ge_var_mul(acc, tab, dg);
+  eq_fixed_terms(acc, B, b, jc);
+}
 __global__ void __launch_bounds__(NT, 2) k_eq_direct(EngineBufs B, const egplan::JobClass* classes, const egplan::VarTerm* terms,
                                                      int class_first, int n_classes) {
   const size_t total = (size_t)n_classes * B.n;
@@ -248,15 +274,8 @@ __global__ void __launch_bounds__(NT, 2) k_eq_direct(EngineBufs B, const egplan:
   for (size_t j = (size_t)blockIdx.x * NT + threadIdx.x; j < total; j += (size_t)gridDim.x * NT) {
     const u32 c = class_first + (u32)(j / B.n), b = (u32)(j % B.n);
     const egplan::JobClass jc = classes[c];
-    const egplan::VarTerm vt = terms[jc.term_first];
-    u32 s[8], dg[8];
-    load_scalar(s, B, b, vt.s, true);
-    sc_recode_radix16(dg, s);
-    ge p, acc;
-    load_pt(p, B.pts, B.cap, vt.slot, b);
-    ge_var_table_build(tab, p);
-    ge_var_mul(acc, tab, dg);
-    eq_fixed_terms(acc, B, b, jc);
+    ge acc;
+    eq_direct(acc, B, b, jc, terms, tab);
     store_pt(B.dpt, B.cap, jc.out_slot, b, acc);
   }
 }
@@ -272,15 +291,8 @@ __global__ void __launch_bounds__(NT, 2) k_eq_direct_h(EngineBufs B, const egpla
   for (size_t j = (size_t)blockIdx.x * NT + threadIdx.x; j < total; j += (size_t)gridDim.x * NT) {
     const u32 c = class_first + (u32)(j / B.n), b = (u32)(j % B.n);
     const egplan::JobClass jc = classes[c];
-    const egplan::VarTerm vt = terms[jc.term_first];
-    u32 s[8], dg[8];
-    load_scalar(s, B, b, vt.s, true);
-    sc_recode_radix16(dg, s);
-    ge p, acc;
-    load_pt(p, B.pts, B.cap, vt.slot, b);
-    ge_var_table_build(tab, p);
-    ge_var_mul(acc, tab, dg);
-    eq_fixed_terms(acc, B, b, jc);
+    ge acc;
+    eq_direct(acc, B, b, jc, terms, tab);
     if (jc.h) {
       const FixedTable th(B.tabH);
       u32 sh[8], dh[EG_COMB_WORDS];
@@ -292,57 +304,60 @@ __global__ void __launch_bounds__(NT, 2) k_eq_direct_h(EngineBufs B, const egpla
   }
 }
 
+// any mix of terms, evaluated term by term: a comb table where the base has one, the radix-16 ladder over `tab` where it has none
+template <int T>
+__device__ __forceinline__ void eq_term_by_term(const EngineBufs& B, u32 b, const egplan::JobClass jc, const egplan::VarTerm* terms,
+                                                WsTable& tab) {
+  ge acc;
+  if (jc.term_count == 0) ge_identity(acc);
+#pragma unroll 1
+  for (u32 t = 0; t < jc.term_count; ++t) {
+    const egplan::VarTerm vt = terms[jc.term_first + t];
+    u32 s[8];
+    load_scalar(s, B, b, vt.s, true);
+    ge part;
+    if (vt.base != 0xffffu) {
+      BaseTable bt{B.btab + ((size_t)vt.base * B.cap + b) * btab_quads<T>()};
+      u64 rows[T];
+      sc_recode_teeth<T>(rows, s);
+      ge_teeth_mul<T>(part, bt, rows);
+    } else {
+      ge p;
+      load_pt(p, B.pts, B.cap, vt.slot, b);
+      u32 dg[8];
+      sc_recode_radix16(dg, s);
+      ge_var_table_build(tab, p);
+      ge_var_mul(part, tab, dg);
+    }
+    if (t == 0) acc = part;
+    else { ge sum; ge_add_full(sum, acc, part); acc = sum; }
+  }
+  eq_fixed_terms(acc, B, b, jc);
+  store_pt(B.dpt, B.cap, jc.out_slot, b, acc);
+}
 template <int T>
 __global__ void __launch_bounds__(NT, 2) k_eq_generic(EngineBufs B, const egplan::JobClass* classes,
                                                       const egplan::VarTerm* terms, int class_first, int n_classes) {
   const size_t total = (size_t)n_classes * B.n;
   WsTable tab;
   tab.init(B.ws);
-  for (size_t j = (size_t)blockIdx.x * NT + threadIdx.x; j < total; j += (size_t)gridDim.x * NT) {
-    const u32 c = class_first + (u32)(j / B.n), b = (u32)(j % B.n);
-    const egplan::JobClass jc = classes[c];
-    ge acc;
-    if (jc.term_count == 0) ge_identity(acc);
-#pragma unroll 1
-    for (u32 t = 0; t < jc.term_count; ++t) {
-      const egplan::VarTerm vt = terms[jc.term_first + t];
-      u32 s[8];
-      load_scalar(s, B, b, vt.s, true);
-      ge part;
-      if (vt.base != 0xffffu) {
-        BaseTable bt{B.btab + ((size_t)vt.base * B.cap + b) * btab_quads<T>()};
-        u64 rows[T];
-        sc_recode_teeth<T>(rows, s);
-        ge_teeth_mul<T>(part, bt, rows);
-      } else {
-        ge p;
-        load_pt(p, B.pts, B.cap, vt.slot, b);
-        u32 dg[8];
-        sc_recode_radix16(dg, s);
-        ge_var_table_build(tab, p);
-        ge_var_mul(part, tab, dg);
-      }
-      if (t == 0) acc = part;
-      else { ge sum; ge_add_full(sum, acc, part); acc = sum; }
-    }
-    eq_fixed_terms(acc, B, b, jc);
-    store_pt(B.dpt, B.cap, jc.out_slot, b, acc);
-  }
+  for (size_t j = (size_t)blockIdx.x * NT + threadIdx.x; j < total; j += (size_t)gridDim.x * NT)
+    eq_term_by_term<T>(B, (u32)(j % B.n), classes[class_first + (u32)(j / B.n)], terms, tab);
 }
 
 // serialize_element (ristretto.rs:88-90) of point slots: the "enc" bytes of derived ciphertexts (range.rs:572), the sum of the
 // choices (choice.rs:83-86).  class: enc_slot -> out_slot.
+__device__ __forceinline__ void point_encode_plain(const EngineBufs& B, u32 b, const egplan::JobClass jc) {
+  ge p;
+  load_pt(p, B.pts, B.cap, jc.enc_slot, b);
+  u32 out[8];
+  ristretto_encode(out, p);
+  store32(B.cmp, B.cap, jc.out_slot, b, out);
+}
 __global__ void __launch_bounds__(NT, 2) k_encode_plain(EngineBufs B, const egplan::JobClass* classes, int class_first, int n_classes) {
   const size_t total = (size_t)n_classes * B.n;
-  for (size_t j = (size_t)blockIdx.x * NT + threadIdx.x; j < total; j += (size_t)gridDim.x * NT) {
-    const u32 c = class_first + (u32)(j / B.n), b = (u32)(j % B.n);
-    const egplan::JobClass jc = classes[c];
-    ge p;
-    load_pt(p, B.pts, B.cap, jc.enc_slot, b);
-    u32 out[8];
-    ristretto_encode(out, p);
-    store32(B.cmp, B.cap, jc.out_slot, b, out);
-  }
+  for (size_t j = (size_t)blockIdx.x * NT + threadIdx.x; j < total; j += (size_t)gridDim.x * NT)
+    point_encode_plain(B, (u32)(j % B.n), classes[class_first + (u32)(j / B.n)]);
 }
 
 // ---- k_encode_batch: serialize_element for all deferred commitments of a ballot with ONE field inversion ------------------------
@@ -389,9 +404,12 @@ __global__ void __launch_bounds__(NT, 2) k_encode_batch(EngineBufs B, const unsi
 }
 
 // ---- k_hash: Merlin transcript programs (proofs/mod.rs:39-57 + the per-proof label schedules) --------------------------------------
-// one transcript program of one ballot; the STROBE state is the lane's word-interleaved LDS column (LdsState)
+// one transcript program of one ballot; the STROBE state is the lane's word-interleaved LDS column (State = LdsStateT of the caller's stride).
+// SAVE_PREFIX: whether OP_SAVE_PREFIX is compiled in.  Only the prefix programs have that op, and they run once per election through
+// k_hash, not per ballot: k_ballot_small leaves it out (its 52-word array would add scratch bytes to every lane of that kernel).
+template <class State, bool SAVE_PREFIX = true>
 __device__ __forceinline__ void hash_program(const EngineBufs& B, u32 b, const egplan::HashInst hi, const egplan::HashOp* ops, u32* lds_col) {
-  Transcript<LdsState> t;
+  Transcript<State> t;
   t.st.base = lds_col;
   t.pos = 0; t.pos_begin = 0; t.cur_flags = 0;
 #pragma unroll 1
@@ -436,11 +454,11 @@ __device__ __forceinline__ void hash_program(const EngineBufs& B, u32 b, const e
         sc_from_wide(e, wide);
         store32(B.chal, B.cap, op.b, b, e);
         if (op.c > 1u) {            // m * e for the folded admissible value of the next equation (ring.rs:338)
-          u32 m[8], t[8];
+          u32 m[8], me[8];
           const u32 z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
           sc_from_u64(m, (u64)op.c);
-          sc_muladd(t, e, m, z);
-          store32(B.chal, B.cap, op.b + 1u, b, t);
+          sc_muladd(me, e, m, z);
+          store32(B.chal, B.cap, op.b + 1u, b, me);
         }
         break;
       }
@@ -455,13 +473,14 @@ __device__ __forceinline__ void hash_program(const EngineBufs& B, u32 b, const e
       case egplan::OP_LOAD_PREFIX:
         merlin_import(t, B.prefixes + (size_t)op.b * 52);
         break;
-      case egplan::OP_SAVE_PREFIX: {
-        u32 w[52];
-        merlin_export(t, w);
+      case egplan::OP_SAVE_PREFIX:            // without SAVE_PREFIX the op is skipped without notice: no per-ballot program may carry it
+        if constexpr (SAVE_PREFIX) {
+          u32 w[52];
+          merlin_export(t, w);
 #pragma unroll 1
-        for (int i = 0; i < 52; ++i) B.prefixes[(size_t)op.b * 52 + i] = w[i];
+          for (int i = 0; i < 52; ++i) B.prefixes[(size_t)op.b * 52 + i] = w[i];
+        }
         break;
-      }
       case egplan::OP_LOAD_STATE: {
 #pragma unroll 1
         for (int i = 0; i < 50; ++i) t.st.wr(i, B.states[((size_t)op.b * 52 + i) * B.cap + b]);
@@ -484,7 +503,7 @@ __global__ void __launch_bounds__(NT) k_hash(EngineBufs B, const egplan::HashIns
   __shared__ u32 lds[50 * NT];
   const size_t j = (size_t)blockIdx.x * NT + threadIdx.x;
   if (j >= (size_t)n_insts * B.n) return;
-  hash_program(B, (u32)(j % B.n), insts[inst_first + (u32)(j / B.n)], ops, lds + threadIdx.x);
+  hash_program<LdsState>(B, (u32)(j % B.n), insts[inst_first + (u32)(j / B.n)], ops, lds + threadIdx.x);
 }
 
 // ---- k_encode_hash: the tail of a stage in one launch, two ballots a lane ------------------------------------------------------------
@@ -536,14 +555,13 @@ __global__ void __launch_bounds__(NT, 3) k_encode_hash(EngineBufs B, const unsig
 #pragma unroll 1
   for (int i = 0; i < nb * n_insts; ++i) {
     const int k = i < n_insts ? i : i - n_insts;
-    hash_program(B, i < n_insts ? j : j + half, insts[inst_first + k], ops, lds + threadIdx.x);
+    hash_program<LdsState>(B, i < n_insts ? j : j + half, insts[inst_first + k], ops, lds + threadIdx.x);
   }
 }
 
 // ---- k_status: first failing check wins, in the reference's order (choice.rs:358-380, quadratic_voting.rs:291-329) ---------------------
-__global__ void __launch_bounds__(NT) k_status(EngineBufs B, const egplan::StatusRule* rules, int n_rules) {
-  const u32 b = blockIdx.x * NT + threadIdx.x;
-  if (b >= B.n) return;
+// a malformed wire item comes before every rule: status = its kind (1 scalar, 2 point) | item << 8
+__device__ __forceinline__ void ballot_status(const EngineBufs& B, u32 b, const egplan::StatusRule* rules, int n_rules) {
   const u32 bad = B.bad_item[b];
   u32 st = 0;
   if (bad != 0xffffffffu) {
@@ -555,6 +573,10 @@ __global__ void __launch_bounds__(NT) k_status(EngineBufs B, const egplan::Statu
     }
   }
   B.status[b] = st;
+}
+__global__ void __launch_bounds__(NT) k_status(EngineBufs B, const egplan::StatusRule* rules, int n_rules) {
+  const u32 b = blockIdx.x * NT + threadIdx.x;
+  if (b < B.n) ballot_status(B, b, rules, n_rules);
 }
 
 // ---- tally: totals[k] += vote[k] over accepted ballots (examples/voting.rs:199-203) ---------------------------------------------------------

@@ -4,9 +4,17 @@
 // handful of ballots the chip is empty and the caller waits for the dependent chain of one lane.  k_ballot_small walks
 // the same plan - wire items, derive classes, table builds, job classes per stage, deferred encodings, hash programs, status rules - with
 // __syncthreads() where the batch engine has kernel boundaries, and gives the long chains (the comb table of a ring base, the ring
-// equations over it, the fixed-base combs) a QUAD of lanes each (ge25519_quad.cuh).  The cold phases run the one-lane device functions
-// of the batch kernels, one lane per item.  Intermediate values live in the engine's work-set buffers, as in the batch path: the
+// equations over it, the fixed-base combs) a QUAD of lanes each (ge25519_quad.cuh).  The cold phases call the per-ballot step bodies
+// of kernels.cuh, the very ones the batch kernels wrap, one lane per item: this file adds the assignment of threads, quads and lanes
+// and the barriers, no second copy of a rule.  Intermediate values live in the engine's work-set buffers, as in the batch path: the
 // tables a quad builds have the layout of BaseTable, so the one-lane families (several bases on one chain, sums of tables) read them.
+//
+// What stays separate from the batch path, on purpose:
+//   - quad_eq_fixed_terms against eq_fixed_terms, and the quad evaluation of the one-table equations (FAM_TABLE1): other table types
+//     (QuadFixedTable, QuadBaseTable) and another multiply (one field element a lane); a shared body would have to branch on its caller;
+//   - the deferred-commitment encode: one inverse a lane here, one batched inversion in k_encode_batch / k_encode_hash (the comment at
+//     the loop says why);
+//   - the comb-table builds on quads (quad_teeth_tables_build / quad_teeth_tables_sum).
 //
 // Block size: 4 lanes per quad of the widest stage, a multiple of 64, at most 256 (one wavefront per SIMD: the kernel is sized for
 // latency, and a block that wide leaves every lane the whole register file, so nothing spills); wider stages loop.
@@ -18,9 +26,8 @@
 namespace eg {
 
 constexpr int SM_MAX_THREADS = 256;
-constexpr int EG_MULTI_GROUP_LDS = 8;                 // terms per shared doubling chain (as the batch path's EG_MULTI_GROUP)
 constexpr int SM_LANES = 64;                          // lanes of the one-lane phases that need LDS or workspace per lane
-constexpr int SM_LDS_WORDS = EG_MULTI_GROUP_LDS * 9 * SM_LANES;      // the largest user: sign vectors of a shared doubling chain
+constexpr int SM_LDS_WORDS = eghost::EG_MULTI_GROUP * 9 * SM_LANES;  // the largest user: sign vectors of a shared doubling chain
 
 struct SmallPlanDev {
   const egplan::WireItem *pt_items, *sc_items;
@@ -95,31 +102,6 @@ struct QuadFixedTable {
   }
 };
 
-// ---- one-lane helpers with LDS behind them -------------------------------------------------------------------------------------------
-struct SmLdsState {            // transcript state, word-interleaved over SM_LANES lanes
-  u32* base;
-  __device__ __forceinline__ u32 rd(int i) const { return base[i * SM_LANES]; }
-  __device__ __forceinline__ void wr(int i, u32 v) { base[i * SM_LANES] = v; }
-};
-struct SmWsTable {             // WsTable with the lane's slice given
-  uint4* base;
-  __device__ __forceinline__ void store(int e, const ge_cached& c) {
-    u32 w[PT_WORDS];
-    fe4_to_words(w, c.YpX, c.YmX, c.Z2, c.T2d);
-#pragma unroll
-    for (int q = 0; q < PT_QUADS; ++q) base[e * PT_QUADS + q] = make_uint4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
-  }
-  __device__ __forceinline__ void load(ge_cached& c, int e) const {
-    u32 w[PT_WORDS];
-#pragma unroll
-    for (int q = 0; q < PT_QUADS; ++q) {
-      const uint4 v = base[e * PT_QUADS + q];
-      w[4 * q] = v.x; w[4 * q + 1] = v.y; w[4 * q + 2] = v.z; w[4 * q + 3] = v.w;
-    }
-    words_to_fe4(c.YpX, c.YmX, c.Z2, c.T2d, w);
-  }
-};
-
 // the fixed-base terms of an equation on a quad (eq_fixed_terms)
 __device__ __forceinline__ void quad_eq_fixed_terms(QuadDev& q, QuadDev::var<fe>& acc, const EngineBufs& B, u32 b, const egplan::JobClass& jc) {
   if (jc.g.kind != egplan::SRC_NONE) {
@@ -138,90 +120,6 @@ __device__ __forceinline__ void quad_eq_fixed_terms(QuadDev& q, QuadDev::var<fe>
   }
 }
 
-// one Merlin program of one ballot (the body of k_hash over an LDS state of SM_LANES columns)
-__device__ __forceinline__ void sm_hash_program(const EngineBufs& B, u32 b, const egplan::HashInst hi, const egplan::HashOp* ops, u32* lds_col) {
-  Transcript<SmLdsState> t;
-  t.st.base = lds_col;
-  t.pos = 0; t.pos_begin = 0; t.cur_flags = 0;
-#pragma unroll 1
-  for (u32 o = 0; o < hi.op_count; ++o) {
-    const egplan::HashOp op = ops[hi.op_first + o];
-    const char* label = reinterpret_cast<const char*>(B.blob) + (op.a >> 12);
-    const int label_len = (int)(op.a & 0xfffu);
-    switch (op.op) {
-      case egplan::OP_NEW:
-        merlin_init(t, label, label_len);
-        break;
-      case egplan::OP_APPEND_BLOB:
-        merlin_append_bytes(t, label, label_len, reinterpret_cast<const char*>(B.blob) + (op.b >> 12), (int)(op.b & 0xfffu));
-        break;
-      case egplan::OP_APPEND_WIRE: {
-        merlin_frame(t, label, label_len, op.c * 32u);
-        strobe_begin_op(t, EG_FLAG_AD);
-#pragma unroll 1
-        for (u32 it = 0; it < op.c; ++it) {
-          u32 w[8];
-          load_wire_item(w, B, b, op.b + it);
-          strobe_absorb_words(t, w, 32);
-        }
-        break;
-      }
-      case egplan::OP_APPEND_CMP: {
-        const u32 n = (op.c == 0xffffu) ? 1u : 2u;
-        merlin_frame(t, label, label_len, n * 32u);
-        strobe_begin_op(t, EG_FLAG_AD);
-        u32 w[8];
-        load32(w, B.cmp, B.cap, op.b, b);
-        strobe_absorb_words(t, w, 32);
-        if (n == 2) { load32(w, B.cmp, B.cap, op.c, b); strobe_absorb_words(t, w, 32); }
-        break;
-      }
-      case egplan::OP_APPEND_U64:
-        merlin_append_u64(t, label, label_len, (u64)op.b);
-        break;
-      case egplan::OP_CHALLENGE: {
-        u32 wide[16], e[8];
-        merlin_challenge64(t, label, label_len, wide);
-        sc_from_wide(e, wide);
-        store32(B.chal, B.cap, op.b, b, e);
-        if (op.c > 1u) {
-          u32 m[8], me[8];
-          const u32 z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-          sc_from_u64(m, (u64)op.c);
-          sc_muladd(me, e, m, z);
-          store32(B.chal, B.cap, op.b + 1u, b, me);
-        }
-        break;
-      }
-      case egplan::OP_CHALLENGE_CHECK: {
-        u32 wide[16], e[8], want[8];
-        merlin_challenge64(t, label, label_len, wide);
-        sc_from_wide(e, wide);
-        load_wire_item(want, B, b, op.b);
-        B.flags[(size_t)op.c * B.cap + b] = sc_eq(e, want) ? 1u : 0u;
-        break;
-      }
-      case egplan::OP_LOAD_PREFIX:
-        merlin_import(t, B.prefixes + (size_t)op.b * 52);
-        break;
-      case egplan::OP_LOAD_STATE: {
-#pragma unroll 1
-        for (int i = 0; i < 50; ++i) t.st.wr(i, B.states[((size_t)op.b * 52 + i) * B.cap + b]);
-        const u32 m = B.states[((size_t)op.b * 52 + 50) * B.cap + b];
-        t.pos = m & 0xffu; t.pos_begin = (m >> 8) & 0xffu; t.cur_flags = (m >> 16) & 0xffu;
-        break;
-      }
-      case egplan::OP_SAVE_STATE: {
-#pragma unroll 1
-        for (int i = 0; i < 50; ++i) B.states[((size_t)op.b * 52 + i) * B.cap + b] = t.st.rd(i);
-        B.states[((size_t)op.b * 52 + 50) * B.cap + b] = t.pos | (t.pos_begin << 8) | (t.cur_flags << 16);
-        break;
-      }
-      default: break;          // OP_SAVE_PREFIX belongs to the prefix programs, which run once per election, not per ballot
-    }
-  }
-}
-
 // ---- the kernel: block b = ballot b ---------------------------------------------------------------------------------------------------
 template <int T>
 __global__ void __launch_bounds__(SM_MAX_THREADS) k_ballot_small(EngineBufs B, SmallPlanDev P) {
@@ -234,45 +132,14 @@ __global__ void __launch_bounds__(SM_MAX_THREADS) k_ballot_small(EngineBufs B, S
   // wire items: decode every point, check every scalar
   if (tid == 0) B.bad_item[b] = 0xffffffffu;
   __syncthreads();
-  for (int k = tid; k < P.n_pt; k += nt) {
-    const egplan::WireItem it = P.pt_items[k];
-    u32 w[8];
-    load_wire_item(w, B, b, it.item);
-    ge p;
-    const bool ok = ristretto_decode(p, w);
-    store_pt(B.pts, B.cap, it.slot, b, p);
-    if (!ok) atomicMin(&B.bad_item[b], (u32)it.item * 4u + 2u);
-  }
-  for (int k = tid; k < P.n_sc; k += nt) {
-    const egplan::WireItem it = P.sc_items[k];
-    u32 w[8];
-    load_wire_item(w, B, b, it.item);
-    if (!sc_is_canonical(w)) atomicMin(&B.bad_item[b], (u32)it.item * 4u + 1u);
-  }
+  for (int k = tid; k < P.n_pt; k += nt) wire_point_decode(B, b, P.pt_items[k]);
+  for (int k = tid; k < P.n_sc; k += nt) wire_scalar_check(B, b, P.sc_items[k]);
   __syncthreads();
 
   // derived points, level by level
   for (int l = 0; l < P.n_levels; ++l) {
     const eghost::LevelDev lv = P.levels[l];
-    for (int k = tid; k < lv.count; k += nt) {
-      const egplan::DeriveClass dc = P.dclasses[lv.first + k];
-      ge acc;
-      ge_identity(acc);
-#pragma unroll 1
-      for (u32 t = 0; t < dc.term_count; ++t) {
-        const egplan::DeriveTerm dt = P.dterms[dc.term_first + t];
-        ge p;
-        if (dt.is_const) load_const_pt(p, B.cpts, dt.slot);
-        else load_pt(p, B.pts, B.cap, dt.slot, b);
-        ge_cached pc;
-        ge_to_cached(pc, p);
-        ge_cached_cneg(pc, dt.neg != 0);
-        ge_p1p1 r;
-        ge_add(r, acc, pc);
-        ge_add_to_p3(acc, r);
-      }
-      store_pt(B.pts, B.cap, dc.out_slot, b, acc);
-    }
+    for (int k = tid; k < lv.count; k += nt) point_derive(B, b, P.dclasses[lv.first + k], P.dterms);
     if (lv.count) __syncthreads();
   }
 
@@ -338,31 +205,8 @@ __global__ void __launch_bounds__(SM_MAX_THREADS) k_ballot_small(EngineBufs B, S
       const int j = j0 + tid;
       if (tid < SM_LANES && j < st.fam_count[eghost::FAM_TABLEN]) {
         const egplan::JobClass jc = P.jobs[st.fam_first[eghost::FAM_TABLEN] + j];
-        const int group = EG_MULTI_GROUP_LDS, nterms = (int)jc.term_count;
         ge acc;
-#pragma unroll 1
-        for (int t0 = 0; t0 < nterms; t0 += group) {
-          const int m = min(group, nterms - t0);
-#pragma unroll 1
-          for (int t = 0; t < m; ++t) {
-            u32 s[8], sg[9];
-            load_scalar(s, B, b, P.vterms[jc.term_first + t0 + t].s, true);
-            sc_teeth_signs<T>(sg, s);
-#pragma unroll
-            for (int w = 0; w < 9; ++w) lds[(t * 9 + w) * SM_LANES + tid] = sg[w];
-          }
-          ge part;
-          ge_teeth_mul_multi<T>(part, m,
-              [&](int t, int col, int& idx, bool& neg) {
-                sc_teeth_column<T>([&](int w) { return lds[(t * 9 + w) * SM_LANES + tid]; }, col, idx, neg);
-              },
-              [&](int t, int idx, ge_cached& e) {
-                const BaseTable bt{B.btab + ((size_t)P.vterms[jc.term_first + t0 + t].base * B.cap + b) * btab_quads<T>()};
-                bt.load(e, idx);
-              });
-          if (t0 == 0) acc = part;
-          else { ge sum; ge_add_full(sum, acc, part); acc = sum; }
-        }
+        eq_shared_chains<T>(acc, B, b, jc, P.vterms, eghost::EG_MULTI_GROUP, [&](int t, int w) -> u32& { return lds[(t * 9 + w) * SM_LANES + tid]; });
         eq_fixed_terms(acc, B, b, jc);
         store_pt(B.dpt, B.cap, jc.out_slot, b, acc);
       }
@@ -376,45 +220,12 @@ __global__ void __launch_bounds__(SM_MAX_THREADS) k_ballot_small(EngineBufs B, S
         const int j = j0 + tid;
         if (tid < SM_LANES && j < count) {
           const int ci = j < st.fam_count[eghost::FAM_DIRECT1] ? first + j : st.fam_first[eghost::FAM_GENERIC] + (j - st.fam_count[eghost::FAM_DIRECT1]);
-          const egplan::JobClass jc = P.jobs[ci];
-          SmWsTable tab{P.ws + ((size_t)b * SM_LANES + tid) * WS_QUADS};
-          ge acc;
-          if (jc.term_count == 0) ge_identity(acc);
-#pragma unroll 1
-          for (u32 t = 0; t < jc.term_count; ++t) {
-            const egplan::VarTerm vt = P.vterms[jc.term_first + t];
-            u32 s[8];
-            load_scalar(s, B, b, vt.s, true);
-            ge part;
-            if (vt.base != 0xffffu) {
-              BaseTable bt{B.btab + ((size_t)vt.base * B.cap + b) * btab_quads<T>()};
-              u64 rows[T];
-              sc_recode_teeth<T>(rows, s);
-              ge_teeth_mul<T>(part, bt, rows);
-            } else {
-              ge p;
-              load_pt(p, B.pts, B.cap, vt.slot, b);
-              u32 dg[8];
-              sc_recode_radix16(dg, s);
-              ge_var_table_build(tab, p);
-              ge_var_mul(part, tab, dg);
-            }
-            if (t == 0) acc = part;
-            else { ge sum; ge_add_full(sum, acc, part); acc = sum; }
-          }
-          eq_fixed_terms(acc, B, b, jc);
-          store_pt(B.dpt, B.cap, jc.out_slot, b, acc);
+          WsTable tab{P.ws + ((size_t)b * SM_LANES + tid) * WS_QUADS};
+          eq_term_by_term<T>(B, b, P.jobs[ci], P.vterms, tab);
         }
       }
     }
-    for (int j = tid; j < st.fam_count[eghost::FAM_ENCODE]; j += nt) {
-      const egplan::JobClass jc = P.jobs[st.fam_first[eghost::FAM_ENCODE] + j];
-      ge p;
-      load_pt(p, B.pts, B.cap, jc.enc_slot, b);
-      u32 out[8];
-      ristretto_encode(out, p);
-      store32(B.cmp, B.cap, jc.out_slot, b, out);
-    }
+    for (int j = tid; j < st.fam_count[eghost::FAM_ENCODE]; j += nt) point_encode_plain(B, b, P.jobs[st.fam_first[eghost::FAM_ENCODE] + j]);
     __syncthreads();
 
     // deferred commitments, out = encode(2P): one lane each.  The batch path encodes a ballot's commitments with ONE inversion in ONE
@@ -434,24 +245,12 @@ __global__ void __launch_bounds__(SM_MAX_THREADS) k_ballot_small(EngineBufs B, S
     // transcripts: the stage's Merlin programs, SM_LANES at a time
     for (int i0 = 0; i0 < st.inst_count; i0 += SM_LANES) {
       const int i = i0 + tid;
-      if (tid < SM_LANES && i < st.inst_count) sm_hash_program(B, b, P.insts[st.inst_first + i], P.ops, lds + tid);
+      if (tid < SM_LANES && i < st.inst_count) hash_program<LdsStateT<SM_LANES>, false>(B, b, P.insts[st.inst_first + i], P.ops, lds + tid);
     }
     __syncthreads();
   }
 
-  // status: first failing check wins (k_status)
-  if (tid == 0) {
-    const u32 bad = B.bad_item[b];
-    u32 stw = 0;
-    if (bad != 0xffffffffu) {
-      stw = (bad & 3u) | ((bad >> 2) << 8);
-    } else {
-#pragma unroll 1
-      for (int r = 0; r < P.n_rules; ++r)
-        if (B.flags[(size_t)P.rules[r].flag_slot * B.cap + b] == 0u) { stw = P.rules[r].status; break; }
-    }
-    B.status[b] = stw;
-  }
+  if (tid == 0) ballot_status(B, b, P.rules, P.n_rules);
 }
 
 }  // namespace eg

@@ -4,7 +4,7 @@
 //
 // The STROBE state lives where the product keeps it: a word-interleaved LDS column per lane, behind
 //   policy 0: LdsState of device_io.cuh itself (stride NT, the column of k_hash and of the prover kernels);
-//   policy 1: a policy of stride 64, the stride of SmLdsState (latency_kernels.cuh: SM_LANES).  That header cannot be included without
+//   policy 1: a policy of stride 64, the stride of k_ballot_small's state (latency_kernels.cuh: SM_LANES).  That header cannot be included without
 //             the whole engine (kernels.cuh, host_plan.hpp), so the policy is restated here.
 // A script needs two transcripts (export -> import, clone), so a block runs half as many lanes as its stride and gives each lane two
 // columns of the one [50][stride] array.

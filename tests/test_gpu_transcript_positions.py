@@ -2,7 +2,7 @@
 tests/transcript_scripts.py (tests/test_transcript_positions_cpu.py says what it holds and proves with the position model that it
 reaches every position) through tests/merlindev - merlin.cuh, unchanged, compiled with the product's flags behind the script
 interpreter that the host build shares - over both LDS strides the product keeps a transcript state in: LdsState itself (stride NT)
-and a policy of SmLdsState's stride.  One script per launch, one case per lane, 65 cases with distinct messages (lanes 0, 63 and 64).
+and a policy of the small-batch kernel's stride (LdsStateT<SM_LANES>).  One script per launch, one case per lane, 65 cases with distinct messages (lanes 0, 63 and 64).
 
 Every output word is compared with the oracle's independent transcript (oracle/transcript.c) and, word for word, with the bound-check
 host build; the expected value never comes from merlin.cuh."""
@@ -23,7 +23,7 @@ pytestmark = pytest.mark.gpu
 
 HERE = Path(__file__).resolve().parent / "merlindev"
 CSRC = HERE.parent.parent / "elastic_elgamal_amd" / "csrc"
-POLICIES = {0: "LdsState, stride NT", 1: "stride of SmLdsState"}
+POLICIES = {0: "LdsState, stride NT", 1: "stride SM_LANES of the small-batch kernel"}
 
 
 def _flags(makefile):
